@@ -8,7 +8,10 @@ windows statically sharded, NO data-path collective (windows never communicate) 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run as a child
 process, before this process has touched a GPU); under an external torchrun it is one of the ranks.
 
-Prints ONE JSON line on rank 0.  Roofline bytes are SURVEY.md 8(d)'s algorithmic bytes and nothing else: every
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`, the workload's `config`); --full adds everything else (CPU baselines and the parity sample, the statistics
+step and per-kernel times behind the rooflines / stages / GCUPS, annotation, device-copy ceiling, secondary legs).
+--dump-outputs DIR writes the last timed step's output arrays.  Roofline bytes are SURVEY.md 8(d)'s algorithmic bytes and nothing else: every
 stage reads its inputs once and writes its outputs once; traceback tiles, decision codes, LDS images and table
 re-scans are intermediates and are NOT counted (DESIGN.md section 5 restates the terms).
 """
@@ -71,14 +74,23 @@ def parse():
     ap.add_argument("--config", default="C3",
                     help="C3 = WGS-shaped tumour/normal 60x/30x (the workload BASELINE.json's metric is quoted on); "
                          "C2 = chr22-shaped 30x/30x (configs[1]); C4, C5")
-    ap.add_argument("--c4-windows", type=int, default=512, help="distinct deep-panel windows of the also.c4_panel leg (0 = skip)")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements (k cascade, other config, host path)")
-    ap.add_argument("--cpu-windows", type=int, default=64, help="oracle sample for cpu_baseline (0 = skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: CPU baselines and the parity sample, the statistics step and HIP-event "
+                         "kernel times behind the rooflines / stages / GCUPS, the annotation timing, the device-copy ceiling and the "
+                         "secondary legs (k cascade, other configs, host path).  Off: set up, warm up, time --steps steps, print the "
+                         "headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (gate, assembly, variant and "
+                         "genotype arrays) as DIR/<array>.npy in float32 / float64, for a fixed seeded sample of the batch's windows "
+                         "(at most 64 MB in all; rank 0's windows when N > 1); DIR/window_id.npy names the seeded window of each row")
+    ap.add_argument("--c4-windows", type=int, default=512, help="--full: distinct deep-panel windows of the also.c4_panel leg (0 = skip)")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary measurements (k cascade, other config, host path)")
+    ap.add_argument("--cpu-windows", type=int, default=64, help="--full: oracle sample for cpu_baseline (0 = skip)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines (and with them the parity sample at N = 1)")
     ap.add_argument("--parity-windows", type=int, default=16,
-                    help="N > 1 only (at N = 1 the cpu_baseline legs' windows are the parity sample): rank 0 runs the oracle on this many "
-                         "of ITS OWN windows before the GPU is initialised and checks the engine's outputs of the last timed step "
-                         "against them (0 = skip)")
+                    help="--full, N > 1 only (at N = 1 the cpu_baseline legs' windows are the parity sample): rank 0 runs the oracle on "
+                         "this many of ITS OWN windows before the GPU is initialised and checks the engine's outputs of the last timed "
+                         "step against them (0 = skip)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes that synthesise windows (0 = min(16, cores))")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="rehearsal of the N > 1 launch path on a box with fewer GPUs than ranks: every rank runs on device "
@@ -87,7 +99,10 @@ def parse():
                          "(`oversubscribed`): it exercises the launcher, the sharding and the rank plumbing -- it is NOT a scaling "
                          "measurement")
     ap.add_argument("--gen-only", action="store_true", help="synthesise the windows (into MA_BENCH_CACHE) and exit: no GPU is touched")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---- algorithmic bytes per window-attempt, by stage ------------------------------------------------
@@ -518,6 +533,42 @@ def parity_check(kept, config, first, lp, n, out_dev, row_of=None):
     return checked, bad, n_flagged[0]
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 0x5EED0D
+
+
+def dump_outputs(path, lp, n, out_dev, window_ids):
+    """--dump-outputs: every output array the timed path hands its caller (gate, assembly, variants, genotypes: the
+    fixed-stride arrays of include/microasm.h) as path/<array>.npy, one row per window, for a fixed seeded sample of the
+    batch's `n` windows -- as many as fit in DUMP_BYTES, all of them when the batch is small enough.  Arrays of 8- and
+    16-bit integers are written as float32, 32-bit integers and f64 as float64 (exact either way); window_id.npy holds the
+    seeded window index of every row.  out_dev = (gate, asm, var, geno) dicts of device byte tensors.  -> bytes written"""
+    import torch
+    from lancet2_amd import capi
+    specs = (capi.gate_out_spec(n), capi.asm_out_spec(lp, n), capi.var_out_spec(lp, n), capi.geno_out_spec(lp, n, 0, debug=False))
+
+    def as_float(dt):
+        dt = np.dtype(dt)
+        return np.float32 if dt.kind in "iu" and dt.itemsize <= 2 else np.float64
+
+    per_window = 8 + sum(sz // n * np.dtype(as_float(dt)).itemsize for spec in specs for dt, sz in spec.values())
+    take = min(n, max(1, DUMP_BYTES // per_window))
+    rows = np.arange(n) if take == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, take, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "window_id.npy"), np.asarray(window_ids, np.float64)[rows])
+    written = 8 * take
+    for dev_, spec in zip(out_dev, specs):
+        sel = None
+        for key, (dt, sz) in spec.items():
+            per = sz // n * np.dtype(dt).itemsize
+            if sel is None:
+                sel = torch.from_numpy(rows).to(dev_[key].device)
+            got = dev_[key][: n * per].view(n, per).index_select(0, sel).cpu().numpy().view(dt).astype(as_float(dt))
+            np.save(os.path.join(path, key + ".npy"), got)
+            written += got.nbytes
+    return written
+
+
 def count_gpus_sysfs():
     """GPUs of this node from the KFD topology (a node with simd_count > 0 is a GPU) -- no torch, no HIP: the process that
     starts the ranks must not have touched a GPU (a re-exec from a GPU-initialised process takes this pool's machines down).
@@ -588,11 +639,11 @@ def main():
     arrs0, n0, nr0 = make_windows(args.config, distinct, first, args.str_every, workers, indices=mine)
     also_arrs = long_arrs = None
     other = {"C3": "C2", "C2": "C3"}.get(args.config)
-    if other and world == 1 and not args.no_also:
+    if other and world == 1 and args.full and not args.no_also:
         also_arrs = make_windows(other, min(distinct, 1024), first, args.str_every, workers)
         long_arrs = make_windows(args.config, min(distinct, 512), first, args.str_every, workers, over=dict(read_len=250))
     c4_arrs = c5_arrs = None
-    if world == 1 and not args.no_also and args.config == "C3":
+    if world == 1 and args.full and not args.no_also and args.config == "C3":
         # BASELINE.json configs[3] and [4]: the deep panel at full depth (500x/500x, 50 bp indels) and the three-sample mode
         c4_arrs = make_windows("C4", min(distinct, args.c4_windows), first, 0, workers) if args.c4_windows > 0 else None
         c5_arrs = make_windows("C5", min(distinct, 2048), first, args.str_every, workers)
@@ -602,9 +653,9 @@ def main():
         return
     cpu = cpu_mt = cpu_c4 = None
     kept = []
-    if world == 1 and not args.no_cpu and args.cpu_windows > 0:
+    if args.full and world == 1 and not args.no_cpu and args.cpu_windows > 0:
         cpu, cpu_mt, cpu_c4, kept = cpu_baselines(args, num_samples)
-    elif world > 1 and rank == 0 and args.parity_windows > 0:  # the checker on a few of rank 0's own windows (never timed)
+    elif args.full and world > 1 and rank == 0 and args.parity_windows > 0:  # the checker on a few of rank 0's own windows (never timed)
         try:
             kept = [_oracle_chunk((args.config, mine[:min(args.parity_windows, len(mine))], 0, num_samples, args.str_every))[2]]
         except Exception as exc:  # (no oracle library on this box: the scaling run goes on without its parity sample, and says so)
@@ -652,10 +703,8 @@ def main():
     a = dev_alloc(capi.asm_out_spec(params, n))
     v = dev_alloc(capi.var_out_spec(params, n))
     q = dev_alloc(capi.geno_out_spec(params, n, nr, debug=False))
-    cx = dev_alloc(capi.cx_out_spec(params, n))
     gs, as_, vs, qs = (capi.fill_struct(capi.GateOut, g), capi.fill_struct(capi.AsmOut, a),
                        capi.fill_struct(capi.VarOut, v), capi.fill_struct(capi.GenoOut, q))
-    cxs = capi.fill_struct(capi.CxOut, cx)
     eng = Engine(params, device=local_rank, memspace=capi.MA_MEM_DEVICE)
     stream = torch.cuda.current_stream(dev)
     eng.set_stream(stream.cuda_stream)
@@ -669,22 +718,26 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # one untimed step in statistics mode: workload counters for the algorithmic-byte model
-    eng.timing_control(3)
-    step()
-    torch.cuda.synchronize(dev)
-    wstats = eng.stats()
+    wstats = {}
+    if args.full:
+        # one untimed step in statistics mode: workload counters for the algorithmic-byte model
+        eng.timing_control(3)
+        step()
+        torch.cuda.synchronize(dev)
+        wstats = eng.stats()
     eng.timing_control(0)
     for _ in range(args.warmup):
         step()
     barrier()
-    eng.timing_control(2)  # HIP events around every kernel, accumulated over the timed region
+    # --full: HIP events around every kernel, accumulated over the timed region; a plain run records no events (mode 0 only
+    # resets the work counters, which then count the timed steps)
+    eng.timing_control(2 if args.full else 0)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    ktimes = eng.kernel_times()
+    ktimes = eng.kernel_times() if args.full else []
     stats = eng.stats()
     # ---- parity sample: the outputs of the LAST timed step for the windows the cpu_baseline legs ran the oracle on ----
     parity = None
@@ -699,40 +752,48 @@ def main():
                              "and compared by its status word only (the host re-submits it with larger buffers)"}
         if pbad:
             parity["first_mismatches"] = pbad[:6]
-    # SEQ_CX / GRAPH_CX annotation of the batch's variants (a "next" row: not part of the metric's
-    # path) -- timed on its own, after the timed region, and reported beside it
-    eng.timing_control(0)
-    eng.annotate_device(b, as_, vs, cxs, 0.41)
-    barrier()
-    eng.timing_control(2)
-    ta = time.perf_counter()
-    for _ in range(args.steps):
+    # ---- --dump-outputs: what the last timed step handed its caller (the arrays are not touched again before this) ----
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, params, n, (g, a, v, q), [mine[j_ % n0] for j_ in range(n)])
+        print(f"bench.py: {dumped / 1e6:.1f} MB of outputs written to {args.dump_outputs}", file=sys.stderr)
+    annot_ms, annot_k, copy_ceiling = None, {}, None
+    if args.full:
+        cx = dev_alloc(capi.cx_out_spec(params, n))
+        cxs = capi.fill_struct(capi.CxOut, cx)
+        # SEQ_CX / GRAPH_CX annotation of the batch's variants (a "next" row: not part of the metric's
+        # path) -- timed on its own, after the timed region, and reported beside it
+        eng.timing_control(0)
         eng.annotate_device(b, as_, vs, cxs, 0.41)
-    barrier()
-    annot_ms = (time.perf_counter() - ta) * 1e3 / max(args.steps, 1)
-    annot_k = {}
-    for name, ms in eng.kernel_times():
-        annot_k[name] = annot_k.get(name, 0.0) + ms / max(args.steps, 1)
-    # ---- the measured device-copy ceiling SURVEY 8(d) asks for beside the 8 TB/s vendor figure: 1 GiB copied device to
-    #      device (read + write = 2 GiB of HBM traffic per copy), after the timed region, torch events on torch's stream ----
-    copy_ceiling = None
-    try:
-        cbytes = 1 << 30
-        csrc_t = torch.empty(cbytes, dtype=torch.uint8, device=dev).fill_(7)
-        cdst_t = torch.empty(cbytes, dtype=torch.uint8, device=dev)
-        for _ in range(3):
-            cdst_t.copy_(csrc_t)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            cdst_t.copy_(csrc_t)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_ceiling = round(2.0 * cbytes * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-        del csrc_t, cdst_t
-    except Exception as ex:  # reported, never fatal: the ceiling is context for the roofline, not part of the metric
+        barrier()
+        eng.timing_control(2)
+        ta = time.perf_counter()
+        for _ in range(args.steps):
+            eng.annotate_device(b, as_, vs, cxs, 0.41)
+        barrier()
+        annot_ms = (time.perf_counter() - ta) * 1e3 / max(args.steps, 1)
+        annot_k = {}
+        for name, ms in eng.kernel_times():
+            annot_k[name] = annot_k.get(name, 0.0) + ms / max(args.steps, 1)
+        # ---- the measured device-copy ceiling SURVEY 8(d) asks for beside the 8 TB/s vendor figure: 1 GiB copied device to
+        #      device (read + write = 2 GiB of HBM traffic per copy), after the timed region, torch events on torch's stream ----
         copy_ceiling = None
-        sys.stderr.write("bench: device-copy ceiling not measured: %r\n" % (ex,))
+        try:
+            cbytes = 1 << 30
+            csrc_t = torch.empty(cbytes, dtype=torch.uint8, device=dev).fill_(7)
+            cdst_t = torch.empty(cbytes, dtype=torch.uint8, device=dev)
+            for _ in range(3):
+                cdst_t.copy_(csrc_t)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                cdst_t.copy_(csrc_t)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_ceiling = round(2.0 * cbytes * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+            del csrc_t, cdst_t
+        except Exception as ex:  # reported, never fatal: the ceiling is context for the roofline, not part of the metric
+            copy_ceiling = None
+            sys.stderr.write("bench: device-copy ceiling not measured: %r\n" % (ex,))
     rank_windows = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if oversub else dev)
@@ -747,44 +808,18 @@ def main():
 
     # ---- workload statistics from the inputs, the results and the engine's counters ----
     status = a["win_status"].view(torch.int32).cpu().numpy().view(np.uint32)
-    nvars = v["win_nvars"].view(torch.int32).cpu().numpy()
-    hap_len = a["hap_len"].view(torch.int32).cpu().numpy().reshape(n, params.max_haps)
     nhaps = a["comp_nhaps"].view(torch.int32).cpu().numpy().reshape(n, params.max_comps)
     ncomp = a["win_ncomp"].view(torch.int32).cpu().numpy()
     gate_approx = g["max_approx"].view(torch.int32).cpu().numpy()
-    alt_len = v["alt_len"].view(torch.int32).cpu().numpy().reshape(n, params.max_vars, params.max_alts)
-    nalts = v["var_nalts"].view(torch.int32).cpu().numpy().reshape(n, params.max_vars)
-    ref_len_v = v["var_ref_len"].view(torch.int32).cpu().numpy().reshape(n, params.max_vars)
     ok = (status & capi.MA_W_NO_HAPLOTYPE) == 0
     assembled = int(ok.sum())
     gated = int((gate_approx >= 25).sum())
     overflowed = int((status & (capi.MA_W_HAP_OVERFLOW | capi.MA_W_LEN_OVERFLOW | capi.MA_W_TABLE_OVERFLOW |
                                 capi.MA_W_VAR_OVERFLOW)).astype(bool).sum())
     steps = max(args.steps, 1)
-    attempts = max(wstats.get("window_attempts", 0), 1)   # of the one statistics step
     R = nr / n
-    Bb = float(arrs["read_off"][-1]) / n
-    W = float(arrs["ref_off"][-1]) / n
     cmask = np.arange(params.max_comps)[None, :] < ncomp[:, None]
     H = float(nhaps[cmask & ok[:, None]].sum()) / max(assembled, 1)
-    hmask = np.arange(params.max_haps)[None, :] < np.where(cmask, nhaps, 0).sum(axis=1)[:, None]
-    L = float(hap_len[hmask & ok[:, None]].sum()) / max(float((hmask & ok[:, None]).sum()), 1.0)
-    vmask = (np.arange(params.max_vars)[None, :] < nvars[:, None]) & ok[:, None]
-    amask = vmask[:, :, None] & (np.arange(params.max_alts)[None, None, :] < nalts[:, :, None])
-    var_bases = float(ref_len_v[vmask].sum() + alt_len[amask].sum()) / max(assembled, 1)
-    pairs_w = stats.get("pairs", 0) / steps / n
-    dp_w = stats.get("dp_pairs", 0) / steps / n
-    read_len = Bb / max(R, 1)
-    st = dict(windows=n, S=params.num_samples, W=W, R=R, B=Bb,
-              N_inst=wstats.get("kmer_instances", 0) / attempts, N_raw=wstats.get("distinct_kmers", 0) / attempts,
-              H=H, L=L, L_ref=L, var_bases=var_bases, n_cigar=params.max_cigar,
-              attempts_per_step=stats.get("window_attempts", 0) / steps, assembled=assembled)
-    st.update(N_slow=wstats.get("slow_instances", 0) / attempts, N_edgeq=wstats.get("edge_queue", 0) / attempts,
-              N_cntq=wstats.get("count_queue", 0) / attempts, N_nodes=wstats.get("nodes_after_lowcov", 0) / attempts,
-              m=read_len, P=pairs_w * n / max(assembled, 1), P_dp=dp_w * n / max(assembled, 1), max_vars=params.max_vars)
-    st.update(poa_band_cells=wstats.get("poa_band_cells", 0) / max(assembled, 1),
-              poa_band_fills=wstats.get("poa_band_fills", 0) / max(assembled, 1))
-    stage_bytes_step = {s: survey_bytes(s, st) * units_per_step(s, st) for s in ("gate", "build", "clean", "poa", "genotype")}
 
     # the metric counts ASSEMBLED windows: those that pass the repeat gate, yield haplotypes and run POA and
     # genotyping too -- counted on every rank and added up (the ranks' shards hold the same mix: blocks of the workload's
@@ -798,165 +833,196 @@ def main():
         assembled_all = int(t_asm.item())
     asm_wps = assembled_all * args.steps / elapsed
 
-    # ---- per-kernel / per-stage times ----
-    agg = {}
-    for name, ms in ktimes:
-        s = agg.setdefault(name, [0.0, 0])
-        s[0] += ms
-        s[1] += 1
-    kernel_ms_per_step = {kname: round(val[0] / args.steps, 3) for kname, val in sorted(agg.items(), key=lambda kv: -kv[1][0])}
-    stage_ms = {}
-    for kname, (tot_ms, _) in agg.items():
-        sname = STAGE_OF.get(kname, "other")
-        stage_ms[sname] = stage_ms.get(sname, 0.0) + tot_ms / args.steps
-    stages = {}
-    for s, ms in sorted(stage_ms.items(), key=lambda kv: -kv[1]):
-        ab = stage_bytes_step.get(s, 0)
-        gbs = ab / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-        stages[s] = {"kernel_ms_per_step": round(ms, 3), "algorithmic_MB_per_step": round(ab / 1e6, 1),
-                     "MB_per_window": round(survey_bytes(s, st) / 1e6, 4), "GB_per_s": round(gbs, 1),
-                     "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 5),
-                     "frac_of_copy_ceiling": round(gbs / copy_ceiling, 5) if copy_ceiling else None}
-    step_bytes = sum(stage_bytes_step.values())
+    # ---- --full: the algorithmic-byte model, per-kernel / per-stage times, rooflines, GCUPS ----
+    nvars = None
+    kernel_ms_per_step = stages = roof = roof_valu = top5 = gcups = step_bytes = None
+    if args.full:
+        nvars = v["win_nvars"].view(torch.int32).cpu().numpy()
+        hap_len = a["hap_len"].view(torch.int32).cpu().numpy().reshape(n, params.max_haps)
+        alt_len = v["alt_len"].view(torch.int32).cpu().numpy().reshape(n, params.max_vars, params.max_alts)
+        nalts = v["var_nalts"].view(torch.int32).cpu().numpy().reshape(n, params.max_vars)
+        ref_len_v = v["var_ref_len"].view(torch.int32).cpu().numpy().reshape(n, params.max_vars)
+        attempts = max(wstats.get("window_attempts", 0), 1)   # of the one statistics step
+        Bb = float(arrs["read_off"][-1]) / n
+        W = float(arrs["ref_off"][-1]) / n
+        hmask = np.arange(params.max_haps)[None, :] < np.where(cmask, nhaps, 0).sum(axis=1)[:, None]
+        L = float(hap_len[hmask & ok[:, None]].sum()) / max(float((hmask & ok[:, None]).sum()), 1.0)
+        vmask = (np.arange(params.max_vars)[None, :] < nvars[:, None]) & ok[:, None]
+        amask = vmask[:, :, None] & (np.arange(params.max_alts)[None, None, :] < nalts[:, :, None])
+        var_bases = float(ref_len_v[vmask].sum() + alt_len[amask].sum()) / max(assembled, 1)
+        pairs_w = stats.get("pairs", 0) / steps / n
+        dp_w = stats.get("dp_pairs", 0) / steps / n
+        read_len = Bb / max(R, 1)
+        st = dict(windows=n, S=params.num_samples, W=W, R=R, B=Bb,
+                  N_inst=wstats.get("kmer_instances", 0) / attempts, N_raw=wstats.get("distinct_kmers", 0) / attempts,
+                  H=H, L=L, L_ref=L, var_bases=var_bases, n_cigar=params.max_cigar,
+                  attempts_per_step=stats.get("window_attempts", 0) / steps, assembled=assembled)
+        st.update(N_slow=wstats.get("slow_instances", 0) / attempts, N_edgeq=wstats.get("edge_queue", 0) / attempts,
+                  N_cntq=wstats.get("count_queue", 0) / attempts, N_nodes=wstats.get("nodes_after_lowcov", 0) / attempts,
+                  m=read_len, P=pairs_w * n / max(assembled, 1), P_dp=dp_w * n / max(assembled, 1), max_vars=params.max_vars)
+        st.update(poa_band_cells=wstats.get("poa_band_cells", 0) / max(assembled, 1),
+                  poa_band_fills=wstats.get("poa_band_fills", 0) / max(assembled, 1))
+        stage_bytes_step = {s: survey_bytes(s, st) * units_per_step(s, st) for s in ("gate", "build", "clean", "poa", "genotype")}
 
-    # ---- dominant kernel: HBM roofline by its stage's SURVEY 8(d) bytes, and a VALU roofline from the PMC pass ----
-    dom = max(agg.items(), key=lambda kv: kv[1][0])[0] if agg else None
-    roof = roof_valu = None
-    prof = {}
-    def prof_is_stale(stamp):  # the counters were taken from another build than the one this run times
-        # by the kernel SOURCES: two builds of the same sources differ as files (hipcc's fat binaries are not reproducible bit
-        # for bit), so the library's own hash -- kept in the stamps for the record -- says nothing about a fresh build
-        return stamp.get("csrc_sha16") != build_stamp()["csrc_sha16"]
+        # ---- per-kernel / per-stage times ----
+        agg = {}
+        for name, ms in ktimes:
+            s = agg.setdefault(name, [0.0, 0])
+            s[0] += ms
+            s[1] += 1
+        kernel_ms_per_step = {kname: round(val[0] / args.steps, 3) for kname, val in sorted(agg.items(), key=lambda kv: -kv[1][0])}
+        stage_ms = {}
+        for kname, (tot_ms, _) in agg.items():
+            sname = STAGE_OF.get(kname, "other")
+            stage_ms[sname] = stage_ms.get(sname, 0.0) + tot_ms / args.steps
+        stages = {}
+        for s, ms in sorted(stage_ms.items(), key=lambda kv: -kv[1]):
+            ab = stage_bytes_step.get(s, 0)
+            gbs = ab / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            stages[s] = {"kernel_ms_per_step": round(ms, 3), "algorithmic_MB_per_step": round(ab / 1e6, 1),
+                         "MB_per_window": round(survey_bytes(s, st) / 1e6, 4), "GB_per_s": round(gbs, 1),
+                         "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 5),
+                         "frac_of_copy_ceiling": round(gbs / copy_ceiling, 5) if copy_ceiling else None}
+        step_bytes = sum(stage_bytes_step.values())
 
-    for cand in ("r6_pmc_per_kernel.json", "r5_pmc_per_kernel.json", "r4_pmc_per_kernel.json", "r3_pmc_per_kernel.json", "r2_pmc_per_kernel.json"):
-        tpath = os.path.join(REPO, "profiles", cand)
-        if os.path.exists(tpath):
-            try:
-                prof = json.load(open(tpath))
-                prof["_file"] = "profiles/" + cand
-                break
-            except Exception:
-                prof = {}
-    if dom:
-        tot_ms, launches = agg[dom]
-        avg_ms = tot_ms / launches
-        launches_per_step = launches / args.steps
-        sname = STAGE_OF.get(dom, "other")
-        own = kernel_bytes(dom, st)
-        bytes_per_launch = (own * units_per_step(sname, st) if own is not None else stage_bytes_step.get(sname, 0)) / max(launches_per_step, 1)
-        ach = bytes_per_launch / (avg_ms * 1e-3) / 1e9
-        pk = prof.get(dom) or next((v for k, v in prof.items() if k.startswith(dom) and isinstance(v, dict)), {})  # (k_align_reg -> k_align_reg2p)
-        roof = {"bound": "hbm", "kernel": dom, "stage": sname, "achieved": round(ach, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 6), "traffic": pk.get("bytes_per_launch"),
-                "traffic_source": prof.get("_file") if pk else None,
-                # the PMC passes are a separate run of this command (rocprofv3 --pmc cannot share a run with the timing);
-                # stale = the kernel sources have changed since those passes were taken
-                "traffic_stale": prof_is_stale(prof.get("_stamp", {})) if pk else None,
-                "avg_launch_ms": round(avg_ms, 4), "launches_per_step": launches_per_step,
-                "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                # SURVEY 8(d) as written: the STAGE's algorithmic bytes per step / the summed time of the stage's kernels
-                "frac_survey": stages.get(sname, {}).get("frac_of_hbm_peak"),
-                # the same two against what a plain device-to-device copy of 1 GiB reaches on this GPU (read + write counted)
-                "copy_ceiling_GBps": copy_ceiling,
-                "frac_of_copy_ceiling": round(ach / copy_ceiling, 6) if copy_ceiling else None,
-                "frac_survey_of_copy_ceiling": stages.get(sname, {}).get("frac_of_copy_ceiling"),
-                "survey_stage_MB_per_step": stages.get(sname, {}).get("algorithmic_MB_per_step"),
-                "survey_stage_kernel_ms_per_step": stages.get(sname, {}).get("kernel_ms_per_step"),
-                "note": "achieved = this kernel's OWN algorithmic bytes per launch (bench.py: kernel_bytes = DESIGN.md section 4's per-window "
-                        "figure x the units one launch processes) / its mean launch time (HIP events on the launch stream); "
-                        "frac_survey = SURVEY 8(d)'s per-window bytes of the kernel's STAGE x the stage's units per step / the summed "
-                        "time of the stage's kernels / peak (what `stages` lists for every stage); "
-                        "roofline_top5 has the same for the five kernels with the most summed time"}
-        if pk.get("valu_insts_per_launch"):
-            lane_ops = pk["valu_insts_per_launch"] * 64.0
-            av = lane_ops / (avg_ms * 1e-3)
-            roof_valu = {"bound": "valu", "kernel": dom, "achieved": round(av / 1e12, 3), "peak": round(VALU_PEAK_LANE_OPS / 1e12, 1),
-                         "unit": "T lane-ops/s", "frac": round(av / VALU_PEAK_LANE_OPS, 4),
-                         "valu_insts_per_launch": pk["valu_insts_per_launch"], "source": prof.get("_file"),
-                         "stale": prof_is_stale(prof.get("_stamp", {})),
-                         "note": "SQ_INSTS_VALU (wave instructions, committed PMC pass of this command) x 64 lanes / this run's "
-                                 "mean launch time; peak = 256 CU x 4 SIMD x 32 lanes x 2.4 GHz"}
+        # ---- dominant kernel: HBM roofline by its stage's SURVEY 8(d) bytes, and a VALU roofline from the PMC pass ----
+        dom = max(agg.items(), key=lambda kv: kv[1][0])[0] if agg else None
+        roof = roof_valu = None
+        prof = {}
+        def prof_is_stale(stamp):  # the counters were taken from another build than the one this run times
+            # by the kernel SOURCES: two builds of the same sources differ as files (hipcc's fat binaries are not reproducible bit
+            # for bit), so the library's own hash -- kept in the stamps for the record -- says nothing about a fresh build
+            return stamp.get("csrc_sha16") != build_stamp()["csrc_sha16"]
 
-    # ---- the five kernels with the most summed time, each priced with its OWN algorithmic bytes (kernel_bytes), beside what the
-    #      committed PMC passes measured for it (traffic, vector instructions, share of wave cycles parked on a wait) ----
-    sq = {}
-    try:
-        sq = json.load(open(os.path.join(REPO, "profiles", "r6_pmc_sq_per_kernel.json")))
-    except Exception:
-        sq = {}
-    top5 = []
-    for kname, (tot_ms, launches) in sorted(agg.items(), key=lambda kv: -kv[1][0])[:5]:
-        per_win = kernel_bytes(kname, st)
-        sname = STAGE_OF.get(kname, "other")
-        units = units_per_step(sname, st)
-        lps = launches / args.steps
-        avg_ms = tot_ms / launches
-        ent = {"kernel": kname, "stage": sname, "avg_launch_ms": round(avg_ms, 4), "launches_per_step": lps,
-               "ms_per_step_summed_over_lanes": round(tot_ms / args.steps, 3)}
-        if per_win is not None:
-            bpl = per_win * units / max(lps, 1)
-            ent.update(algorithmic_bytes_per_window=int(per_win), algorithmic_bytes_per_launch=int(bpl),
-                       achieved_GBps=round(bpl / (avg_ms * 1e-3) / 1e9, 2), frac_of_hbm_peak=round(bpl / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5))
-        pk = prof.get(kname) or next((v_ for k_, v_ in prof.items() if k_.startswith(kname) and isinstance(v_, dict)), {})
-        if pk:
-            ent.update(traffic_bytes_per_launch=pk.get("bytes_per_launch"), valu_insts_per_launch=pk.get("valu_insts_per_launch"),
-                       counters_stale=prof_is_stale(prof.get("_stamp", {})), counters_source=prof.get("_file"))
+        for cand in ("r6_pmc_per_kernel.json", "r5_pmc_per_kernel.json", "r4_pmc_per_kernel.json", "r3_pmc_per_kernel.json", "r2_pmc_per_kernel.json"):
+            tpath = os.path.join(REPO, "profiles", cand)
+            if os.path.exists(tpath):
+                try:
+                    prof = json.load(open(tpath))
+                    prof["_file"] = "profiles/" + cand
+                    break
+                except Exception:
+                    prof = {}
+        if dom:
+            tot_ms, launches = agg[dom]
+            avg_ms = tot_ms / launches
+            launches_per_step = launches / args.steps
+            sname = STAGE_OF.get(dom, "other")
+            own = kernel_bytes(dom, st)
+            bytes_per_launch = (own * units_per_step(sname, st) if own is not None else stage_bytes_step.get(sname, 0)) / max(launches_per_step, 1)
+            ach = bytes_per_launch / (avg_ms * 1e-3) / 1e9
+            pk = prof.get(dom) or next((v for k, v in prof.items() if k.startswith(dom) and isinstance(v, dict)), {})  # (k_align_reg -> k_align_reg2p)
+            roof = {"bound": "hbm", "kernel": dom, "stage": sname, "achieved": round(ach, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach / HBM_PEAK_GBS, 6), "traffic": pk.get("bytes_per_launch"),
+                    "traffic_source": prof.get("_file") if pk else None,
+                    # the PMC passes are a separate run of this command (rocprofv3 --pmc cannot share a run with the timing);
+                    # stale = the kernel sources have changed since those passes were taken
+                    "traffic_stale": prof_is_stale(prof.get("_stamp", {})) if pk else None,
+                    "avg_launch_ms": round(avg_ms, 4), "launches_per_step": launches_per_step,
+                    "algorithmic_bytes_per_launch": int(bytes_per_launch),
+                    # SURVEY 8(d) as written: the STAGE's algorithmic bytes per step / the summed time of the stage's kernels
+                    "frac_survey": stages.get(sname, {}).get("frac_of_hbm_peak"),
+                    # the same two against what a plain device-to-device copy of 1 GiB reaches on this GPU (read + write counted)
+                    "copy_ceiling_GBps": copy_ceiling,
+                    "frac_of_copy_ceiling": round(ach / copy_ceiling, 6) if copy_ceiling else None,
+                    "frac_survey_of_copy_ceiling": stages.get(sname, {}).get("frac_of_copy_ceiling"),
+                    "survey_stage_MB_per_step": stages.get(sname, {}).get("algorithmic_MB_per_step"),
+                    "survey_stage_kernel_ms_per_step": stages.get(sname, {}).get("kernel_ms_per_step"),
+                    "note": "achieved = this kernel's OWN algorithmic bytes per launch (bench.py: kernel_bytes = DESIGN.md section 4's per-window "
+                            "figure x the units one launch processes) / its mean launch time (HIP events on the launch stream); "
+                            "frac_survey = SURVEY 8(d)'s per-window bytes of the kernel's STAGE x the stage's units per step / the summed "
+                            "time of the stage's kernels / peak (what `stages` lists for every stage); "
+                            "roofline_top5 has the same for the five kernels with the most summed time"}
             if pk.get("valu_insts_per_launch"):
-                ent["valu_frac"] = round(pk["valu_insts_per_launch"] * 64.0 / (avg_ms * 1e-3) / VALU_PEAK_LANE_OPS, 4)
-            if pk.get("bytes_per_launch") and per_win is not None:
-                ent["traffic_over_algorithmic"] = round(pk["bytes_per_launch"] / max(bpl, 1), 2)
-        sk = sq.get(kname) or next((v_ for k_, v_ in sq.items() if k_.startswith(kname) and isinstance(v_, dict)), {})
-        if sk.get("SQ_WAVE_CYCLES"):
-            ent["wait_any_share"] = round(sk.get("SQ_WAIT_ANY", 0) / sk["SQ_WAVE_CYCLES"], 3)
-        top5.append(ent)
+                lane_ops = pk["valu_insts_per_launch"] * 64.0
+                av = lane_ops / (avg_ms * 1e-3)
+                roof_valu = {"bound": "valu", "kernel": dom, "achieved": round(av / 1e12, 3), "peak": round(VALU_PEAK_LANE_OPS / 1e12, 1),
+                             "unit": "T lane-ops/s", "frac": round(av / VALU_PEAK_LANE_OPS, 4),
+                             "valu_insts_per_launch": pk["valu_insts_per_launch"], "source": prof.get("_file"),
+                             "stale": prof_is_stale(prof.get("_stamp", {})),
+                             "note": "SQ_INSTS_VALU (wave instructions, committed PMC pass of this command) x 64 lanes / this run's "
+                                     "mean launch time; peak = 256 CU x 4 SIMD x 32 lanes x 2.4 GHz"}
 
-    # ---- GCUPS of the two DP stages: cells of the statistics step / the summed time of the
-    #      kernels that compute them in the timed region; beside it the vector lane-operations each cell cost (committed
-    #      SQ_INSTS_VALU pass of this command) -- the VALU roofline is what bounds integer DP on this chip, not MFMA ----
-    def pmc_insts_per_step(prefixes):
-        """wave-level VALU instructions per step of every profiled kernel whose name starts with one of `prefixes`"""
-        steps_prof = prof.get("_stamp", {}).get("steps_profiled", 5)  # 2 timed + 2 warm-up + 1 statistics step
-        tot, found = 0.0, False
-        for k_, v_ in prof.items():
-            if isinstance(v_, dict) and not k_.startswith("_") and k_.startswith(tuple(prefixes)) and v_.get("valu_insts_per_launch"):
-                tot += v_["valu_insts_per_launch"] * v_.get("launches", 0)
-                found = True
-        return tot / steps_prof if found else None
+        # ---- the five kernels with the most summed time, each priced with its OWN algorithmic bytes (kernel_bytes), beside what the
+        #      committed PMC passes measured for it (traffic, vector instructions, share of wave cycles parked on a wait) ----
+        sq = {}
+        try:
+            sq = json.load(open(os.path.join(REPO, "profiles", "r6_pmc_sq_per_kernel.json")))
+        except Exception:
+            sq = {}
+        top5 = []
+        for kname, (tot_ms, launches) in sorted(agg.items(), key=lambda kv: -kv[1][0])[:5]:
+            per_win = kernel_bytes(kname, st)
+            sname = STAGE_OF.get(kname, "other")
+            units = units_per_step(sname, st)
+            lps = launches / args.steps
+            avg_ms = tot_ms / launches
+            ent = {"kernel": kname, "stage": sname, "avg_launch_ms": round(avg_ms, 4), "launches_per_step": lps,
+                   "ms_per_step_summed_over_lanes": round(tot_ms / args.steps, 3)}
+            if per_win is not None:
+                bpl = per_win * units / max(lps, 1)
+                ent.update(algorithmic_bytes_per_window=int(per_win), algorithmic_bytes_per_launch=int(bpl),
+                           achieved_GBps=round(bpl / (avg_ms * 1e-3) / 1e9, 2), frac_of_hbm_peak=round(bpl / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5))
+            pk = prof.get(kname) or next((v_ for k_, v_ in prof.items() if k_.startswith(kname) and isinstance(v_, dict)), {})
+            if pk:
+                ent.update(traffic_bytes_per_launch=pk.get("bytes_per_launch"), valu_insts_per_launch=pk.get("valu_insts_per_launch"),
+                           counters_stale=prof_is_stale(prof.get("_stamp", {})), counters_source=prof.get("_file"))
+                if pk.get("valu_insts_per_launch"):
+                    ent["valu_frac"] = round(pk["valu_insts_per_launch"] * 64.0 / (avg_ms * 1e-3) / VALU_PEAK_LANE_OPS, 4)
+                if pk.get("bytes_per_launch") and per_win is not None:
+                    ent["traffic_over_algorithmic"] = round(pk["bytes_per_launch"] / max(bpl, 1), 2)
+            sk = sq.get(kname) or next((v_ for k_, v_ in sq.items() if k_.startswith(kname) and isinstance(v_, dict)), {})
+            if sk.get("SQ_WAVE_CYCLES"):
+                ent["wait_any_share"] = round(sk.get("SQ_WAIT_ANY", 0) / sk["SQ_WAVE_CYCLES"], 3)
+            top5.append(ent)
 
-    def gcups_entry(cells, knames, what, extra_kernels=()):
-        ms = sum(agg[k_][0] for k_ in knames if k_ in agg) / args.steps
-        if cells <= 0 or ms <= 0:
-            return None
-        ent = {"cells_per_step": int(cells), "cells": what, "kernels": [k_ for k_ in knames if k_ in agg],
-               "kernel_ms_per_step_summed_over_lanes": round(ms, 3), "GCUPS": round(cells / (ms * 1e-3) / 1e9, 1)}
-        if extra_kernels:
-            ms2 = ms + sum(agg[k_][0] for k_ in extra_kernels if k_ in agg) / args.steps
-            ent["GCUPS_incl_" + "_".join(k_.replace("k_", "") for k_ in extra_kernels if k_ in agg)] = round(cells / (ms2 * 1e-3) / 1e9, 1)
-        insts = pmc_insts_per_step(knames)
-        if insts:
-            ent.update(valu_lane_ops_per_cell=round(insts * 64.0 / cells, 1),
-                       valu_frac_of_peak=round(insts * 64.0 / (ms * 1e-3) / VALU_PEAK_LANE_OPS, 4),
-                       valu_peak_T_lane_ops_per_s=round(VALU_PEAK_LANE_OPS / 1e12, 1),
-                       counters_source=prof.get("_file"), counters_stale=prof_is_stale(prof.get("_stamp", {})))
-        return ent
+        # ---- GCUPS of the two DP stages: cells of the statistics step / the summed time of the
+        #      kernels that compute them in the timed region; beside it the vector lane-operations each cell cost (committed
+        #      SQ_INSTS_VALU pass of this command) -- the VALU roofline is what bounds integer DP on this chip, not MFMA ----
+        def pmc_insts_per_step(prefixes):
+            """wave-level VALU instructions per step of every profiled kernel whose name starts with one of `prefixes`"""
+            steps_prof = prof.get("_stamp", {}).get("steps_profiled", 5)  # 2 timed + 2 warm-up + 1 statistics step
+            tot, found = 0.0, False
+            for k_, v_ in prof.items():
+                if isinstance(v_, dict) and not k_.startswith("_") and k_.startswith(tuple(prefixes)) and v_.get("valu_insts_per_launch"):
+                    tot += v_["valu_insts_per_launch"] * v_.get("launches", 0)
+                    found = True
+            return tot / steps_prof if found else None
 
-    gcups = {
-        "read_aligner": gcups_entry(wstats.get("aln_dp_cells", 0), ("k_align_reg", "k_align_wave", "k_align_gen"),
-                                    "rows x region width of every read x haplotype pair that ran the DP (a19); the kernels compute "
-                                    "their width class's cells in chunks of eight up to the widest region of a group", ("k_align_tb",)),
-        "poa_band": gcups_entry(wstats.get("poa_band_cells", 0), ("k_msa_band", "k_poa"),
-                                "rows x band columns of every banded haplotype <-> graph fill that ran (a18); alignments written "
-                                "down in closed form have no cells"),
-        "poa_alignments_per_step": wstats.get("poa_alignments", 0), "poa_closed_form_per_step": wstats.get("poa_direct_alignments", 0),
-        "poa_band_fills_per_step": wstats.get("poa_band_fills", 0), "poa_full_fill_cells_per_step": wstats.get("poa_full_cells", 0),
-        "dp_pairs_per_step": wstats.get("dp_pairs", 0),
-        "note": "GCUPS = 1e9 cell updates per second of kernel time; under concurrent lanes the kernels' times are stretched by sharing "
-                "the chip (profiles/*_bench_single_lane.json has the unshared times)"}
+        def gcups_entry(cells, knames, what, extra_kernels=()):
+            ms = sum(agg[k_][0] for k_ in knames if k_ in agg) / args.steps
+            if cells <= 0 or ms <= 0:
+                return None
+            ent = {"cells_per_step": int(cells), "cells": what, "kernels": [k_ for k_ in knames if k_ in agg],
+                   "kernel_ms_per_step_summed_over_lanes": round(ms, 3), "GCUPS": round(cells / (ms * 1e-3) / 1e9, 1)}
+            if extra_kernels:
+                ms2 = ms + sum(agg[k_][0] for k_ in extra_kernels if k_ in agg) / args.steps
+                ent["GCUPS_incl_" + "_".join(k_.replace("k_", "") for k_ in extra_kernels if k_ in agg)] = round(cells / (ms2 * 1e-3) / 1e9, 1)
+            insts = pmc_insts_per_step(knames)
+            if insts:
+                ent.update(valu_lane_ops_per_cell=round(insts * 64.0 / cells, 1),
+                           valu_frac_of_peak=round(insts * 64.0 / (ms * 1e-3) / VALU_PEAK_LANE_OPS, 4),
+                           valu_peak_T_lane_ops_per_s=round(VALU_PEAK_LANE_OPS / 1e12, 1),
+                           counters_source=prof.get("_file"), counters_stale=prof_is_stale(prof.get("_stamp", {})))
+            return ent
+
+        gcups = {
+            "read_aligner": gcups_entry(wstats.get("aln_dp_cells", 0), ("k_align_reg", "k_align_wave", "k_align_gen"),
+                                        "rows x region width of every read x haplotype pair that ran the DP (a19); the kernels compute "
+                                        "their width class's cells in chunks of eight up to the widest region of a group", ("k_align_tb",)),
+            "poa_band": gcups_entry(wstats.get("poa_band_cells", 0), ("k_msa_band", "k_poa"),
+                                    "rows x band columns of every banded haplotype <-> graph fill that ran (a18); alignments written "
+                                    "down in closed form have no cells"),
+            "poa_alignments_per_step": wstats.get("poa_alignments", 0), "poa_closed_form_per_step": wstats.get("poa_direct_alignments", 0),
+            "poa_band_fills_per_step": wstats.get("poa_band_fills", 0), "poa_full_fill_cells_per_step": wstats.get("poa_full_cells", 0),
+            "dp_pairs_per_step": wstats.get("dp_pairs", 0),
+            "note": "GCUPS = 1e9 cell updates per second of kernel time; under concurrent lanes the kernels' times are stretched by sharing "
+                    "the chip (profiles/*_bench_single_lane.json has the unshared times)"}
 
     # ---- secondary measurements (never `value`) ----
     also = {}
     eng.close()  # its workspaces are grow-only shares of the whole HBM: one engine at a time
-    if world == 1 and not args.no_also:
+    if world == 1 and args.full and not args.no_also:
         # (1) the default k cascade (min_k 13 .. max_k 127, graph_params.h:11-26) on the same windows
         cparams = capi.default_params()
         cparams.num_samples = num_samples
@@ -1255,28 +1321,31 @@ def main():
                        "oversubscribed": (f"REHEARSAL: {world} ranks share {torch.cuda.device_count()} device(s), gloo barrier -- exercises "
                                           "the launch / sharding path, not a scaling measurement") if oversub else None,
                        "input_synthesis_s": round(t_gen, 1)},
-            "roofline": roof, "roofline_valu": roof_valu, "roofline_top5": top5, "gcups": gcups, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_mt,
-            "parity_sample": parity,
-            "step_algorithmic": {"MB_per_step": round(step_bytes / 1e6, 1),
-                                 "GB_per_s": round(step_bytes / (elapsed / args.steps) / 1e9, 1),
-                                 "frac_of_hbm_peak": round(step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
-                                 "copy_ceiling_GBps": copy_ceiling,
-                                 "frac_of_copy_ceiling": round(step_bytes / (elapsed / args.steps) / 1e9 / copy_ceiling, 5) if copy_ceiling else None},
             "build": build_stamp(),  # what this run loaded: tools/pmc_per_kernel.py stamps the counters of a PMC pass with it
-            "kernel_ms_per_step": kernel_ms_per_step, "stages": stages,
-            "work": {"pairs_per_window": round(pairs_w, 1), "dp_pairs_per_window": round(dp_w, 1),
-                     "dp_pairs_by_region_width": {k_: round(stats.get(k_, 0) / steps / n, 2)
-                                                  for k_ in ("dp_w41", "dp_w65", "dp_w129", "dp_wide")},
-                     "kmer_instances_per_attempt": round(st["N_inst"], 1), "distinct_kmers_per_attempt": round(st["N_raw"], 1),
-                     "nodes_after_lowcov_per_attempt": round(wstats.get("nodes_after_lowcov", 0) / attempts, 1),
-                     "slow_instances_per_attempt": round(wstats.get("slow_instances", 0) / attempts, 1),
-                     "mean_haplotype_len": round(L, 1), "variant_bases_per_assembled_window": round(var_bases, 1),
-                     "mean_read_len": round(read_len, 1)},
-            # SURVEY 8 f3 (next row), outside the metric's timed region: ma_annotate_batch over the same batch
-            "also": also or None,
-            "annotation": {"ms_per_step": round(annot_ms, 3), "variants_per_window": round(float(nvars.sum()) / n, 2),
-                           "kernel_ms_per_step": {k_: round(v_, 3) for k_, v_ in annot_k.items()}},
         }
+        if args.full:  # (the figures a plain run does not take)
+            out.update({
+                "roofline": roof, "roofline_valu": roof_valu, "roofline_top5": top5, "gcups": gcups, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_mt,
+                "parity_sample": parity,
+                "step_algorithmic": {"MB_per_step": round(step_bytes / 1e6, 1),
+                                     "GB_per_s": round(step_bytes / (elapsed / args.steps) / 1e9, 1),
+                                     "frac_of_hbm_peak": round(step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
+                                     "copy_ceiling_GBps": copy_ceiling,
+                                     "frac_of_copy_ceiling": round(step_bytes / (elapsed / args.steps) / 1e9 / copy_ceiling, 5) if copy_ceiling else None},
+                "kernel_ms_per_step": kernel_ms_per_step, "stages": stages,
+                "work": {"pairs_per_window": round(pairs_w, 1), "dp_pairs_per_window": round(dp_w, 1),
+                         "dp_pairs_by_region_width": {k_: round(stats.get(k_, 0) / steps / n, 2)
+                                                      for k_ in ("dp_w41", "dp_w65", "dp_w129", "dp_wide")},
+                         "kmer_instances_per_attempt": round(st["N_inst"], 1), "distinct_kmers_per_attempt": round(st["N_raw"], 1),
+                         "nodes_after_lowcov_per_attempt": round(wstats.get("nodes_after_lowcov", 0) / attempts, 1),
+                         "slow_instances_per_attempt": round(wstats.get("slow_instances", 0) / attempts, 1),
+                         "mean_haplotype_len": round(L, 1), "variant_bases_per_assembled_window": round(var_bases, 1),
+                         "mean_read_len": round(read_len, 1)},
+                # SURVEY 8 f3 (next row), outside the metric's timed region: ma_annotate_batch over the same batch
+                "also": also or None,
+                "annotation": {"ms_per_step": round(annot_ms, 3), "variants_per_window": round(float(nvars.sum()) / n, 2),
+                               "kernel_ms_per_step": {k_: round(v_, 3) for k_, v_ in annot_k.items()}},
+            })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

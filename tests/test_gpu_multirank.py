@@ -19,7 +19,7 @@ def test_two_ranks_rehearsed_on_one_device():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "1", "--warmup", "1",
-           "--no-cpu", "--no-also", "--windows", "1024", "--distinct", "1024", "--parity-windows", "8"]
+           "--full", "--no-cpu", "--no-also", "--windows", "1024", "--distinct", "1024", "--parity-windows", "8"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=REPO, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])

@@ -8,7 +8,7 @@ python3 bench.py --no-cpu --no-also --gen-only --windows 8192 --distinct 8192 > 
 for rep in 1 2; do
 for gb in 0 11; do
   if [ $gb = 0 ]; then unset MA_WS_GB; else export MA_WS_GB=$gb; fi
-  timeout 300 python3 bench.py --no-cpu --no-also --gen-workers 1 --windows 8192 --distinct 8192 --steps 16 2> $O/err_$gb.txt | tail -1 > $O/b_$gb.json
+  timeout 300 python3 bench.py --full --no-cpu --no-also --gen-workers 1 --windows 8192 --distinct 8192 --steps 16 2> $O/err_$gb.txt | tail -1 > $O/b_$gb.json
   python3 - <<P
 import json
 try:

@@ -7,8 +7,8 @@ mkdir -p $O
 timeout 1500 python3 -m pytest tests/test_gpu_multirank.py tests/test_gpu_aligner.py -x -q -m gpu > $O/tests.txt 2>&1
 tail -5 $O/tests.txt
 export MA_BENCH_CACHE=/tmp/ma_bench_cache
-timeout 900 python3 bench.py --no-cpu --no-also --steps 4 2> $O/bench.err | tail -1 > $O/bench_short.json
-MA_STREAMS=1 timeout 900 python3 bench.py --no-cpu --no-also --steps 4 2>> $O/bench.err | tail -1 > $O/bench_short_single_lane.json
+timeout 900 python3 bench.py --full --no-cpu --no-also --steps 4 2> $O/bench.err | tail -1 > $O/bench_short.json
+MA_STREAMS=1 timeout 900 python3 bench.py --full --no-cpu --no-also --steps 4 2>> $O/bench.err | tail -1 > $O/bench_short_single_lane.json
 python3 - <<'PY'
 import json
 for f in ("bench_short.json", "bench_short_single_lane.json"):

@@ -7,7 +7,7 @@ export MA_BENCH_CACHE=/tmp/ma_bench_cache
 python3 bench.py --no-cpu --no-also --gen-only > $O/gen.log 2>&1
 run() {  # label, env...
   local label=$1; shift
-  env "$@" timeout 600 python3 bench.py --no-cpu --no-also --steps 6 2>> $O/err.txt | tail -1 > $O/$label.json
+  env "$@" timeout 600 python3 bench.py --full --no-cpu --no-also --steps 6 2>> $O/err.txt | tail -1 > $O/$label.json
   python3 - "$O/$label.json" "$label" <<'PY'
 import json, sys
 try:

@@ -5,7 +5,7 @@ O=gpurun_out/r6_knobs2
 mkdir -p $O
 python3 bench.py --no-cpu --no-also --gen-only > $O/gen.log 2>&1
 run() {
-  timeout 300 python3 bench.py --no-cpu --no-also --gen-workers 1 2>$O/err.txt | tail -1 > $O/b.json
+  timeout 300 python3 bench.py --full --no-cpu --no-also --gen-workers 1 2>$O/err.txt | tail -1 > $O/b.json
   python3 - <<P
 import json
 d=json.load(open("$O/b.json"))

@@ -5,7 +5,7 @@ O=gpurun_out/r6_lanes_legs
 mkdir -p $O
 for lanes in 2 0; do
   if [ $lanes = 0 ]; then unset MA_STREAMS; else export MA_STREAMS=$lanes; fi
-  timeout 900 python3 bench.py --no-cpu 2>$O/err_$lanes.txt | tail -1 > $O/b_$lanes.json
+  timeout 900 python3 bench.py --full --no-cpu 2>$O/err_$lanes.txt | tail -1 > $O/b_$lanes.json
   python3 - <<P
 import json
 d=json.load(open("$O/b_$lanes.json"))

@@ -4,10 +4,10 @@ export MA_BENCH_CACHE=/tmp/ma_bench_cache
 O=gpurun_out/r6_onechunk
 mkdir -p $O
 python3 bench.py --no-cpu --no-also --gen-only > $O/gen.log 2>&1
-MA_VERBOSE=1 timeout 300 python3 bench.py --no-cpu --no-also --gen-workers 1 --steps 1 --warmup 1 2>&1 | grep "msa:\|assemble:" | cut -c1-150 | sort | uniq -c | sort -rn | head -6
+MA_VERBOSE=1 timeout 300 python3 bench.py --full --no-cpu --no-also --gen-workers 1 --steps 1 --warmup 1 2>&1 | grep "msa:\|assemble:" | cut -c1-150 | sort | uniq -c | sort -rn | head -6
 for rep in 1 2 3; do
   for lanes in 4 1; do
-    MA_STREAMS=$lanes timeout 300 python3 bench.py --no-cpu --no-also --gen-workers 1 2>$O/err.txt | tail -1 > $O/b_${lanes}_$rep.json
+    MA_STREAMS=$lanes timeout 300 python3 bench.py --full --no-cpu --no-also --gen-workers 1 2>$O/err.txt | tail -1 > $O/b_${lanes}_$rep.json
     python3 - <<P
 import json
 try:

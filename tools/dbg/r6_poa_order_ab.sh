@@ -9,7 +9,7 @@ python3 bench.py --no-cpu --no-also --gen-only > $O/gen.log 2>&1
 for rep in 1 2; do
   for ord in 1 0; do
     for lanes in 4 1; do
-      MA_POA_ORDER=$ord MA_STREAMS=$lanes timeout 300 python3 bench.py --no-cpu --no-also --gen-workers 1 2>/dev/null | tail -1 > $O/b_${ord}_${lanes}_$rep.json
+      MA_POA_ORDER=$ord MA_STREAMS=$lanes timeout 300 python3 bench.py --full --no-cpu --no-also --gen-workers 1 2>/dev/null | tail -1 > $O/b_${ord}_${lanes}_$rep.json
       python3 - <<P
 import json
 d=json.load(open("$O/b_${ord}_${lanes}_$rep.json"))

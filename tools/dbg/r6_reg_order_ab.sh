@@ -6,7 +6,7 @@ mkdir -p $O
 timeout 900 python3 -m pytest tests/test_gpu_aligner.py tests/test_gpu_parity.py -x -q -m gpu -k "align or geno or process or pairs" 2>&1 | tail -2
 python3 bench.py --no-cpu --no-also --gen-only > $O/gen.log 2>&1
 run() {
-  timeout 300 python3 bench.py --no-cpu --no-also --gen-workers 1 2>$O/err.txt | tail -1 > $O/b.json
+  timeout 300 python3 bench.py --full --no-cpu --no-also --gen-workers 1 2>$O/err.txt | tail -1 > $O/b.json
   python3 - <<P
 import json
 d=json.load(open("$O/b.json"))

@@ -7,7 +7,7 @@ python3 bench.py --no-cpu --no-also --gen-only > /dev/null 2>&1
 for lib in ${VOTE_LIBS:-libmicroasm.so libmicroasm_vs1.so libmicroasm_vs2.so libmicroasm_vs3.so}; do
   MA_LIB=$PWD/lancet2_amd/$lib MA_STREAMS=1 python3 - >> gpurun_out/r5b/vote_phases.txt 2>/dev/null <<PY
 import sys, json, subprocess, os
-r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--no-cpu", "--no-also"], capture_output=True, text=True)
+r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--no-cpu", "--no-also"], capture_output=True, text=True)
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
 if line:
     d = json.loads(line[-1]); print("$lib", "k_vote", d["kernel_ms_per_step"].get("k_vote"), "ms per 16384 windows single-lane; parity_sample", d.get("parity_sample"))

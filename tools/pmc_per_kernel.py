@@ -1,10 +1,10 @@
 """Per-kernel PMC figures from separate rocprofv3 --pmc passes of the SAME bench.py command (FETCH_SIZE, WRITE_SIZE and
 SQ_INSTS_VALU do not share a pass on gfx950, MI355X_MICROARCH.md "rocprofv3 PMC slots"):
 
-  rocprofv3 --pmc FETCH_SIZE    --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 2 --no-cpu --no-also
-  rocprofv3 --pmc WRITE_SIZE    --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 2 --no-cpu --no-also
-  rocprofv3 --pmc SQ_INSTS_VALU --kernel-trace --output-format csv -d gpurun_out/pmc_valu  -- python3 bench.py --steps 2 --no-cpu --no-also
-  python3 tools/pmc_per_kernel.py gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_valu profiles/r2_pmc_per_kernel.json
+  rocprofv3 --pmc FETCH_SIZE    --kernel-trace --output-format csv -d build/pmc_fetch -- python3 bench.py --full --steps 2 --no-cpu --no-also
+  rocprofv3 --pmc WRITE_SIZE    --kernel-trace --output-format csv -d build/pmc_write -- python3 bench.py --full --steps 2 --no-cpu --no-also
+  rocprofv3 --pmc SQ_INSTS_VALU --kernel-trace --output-format csv -d build/pmc_valu  -- python3 bench.py --full --steps 2 --no-cpu --no-also
+  python3 tools/pmc_per_kernel.py build/pmc_fetch build/pmc_write build/pmc_valu profiles/r2_pmc_per_kernel.json
 
 Units / corrections (MI355X_MICROARCH.md, "HBM"): FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE tallies
 128-byte requests at 64 bytes, so reads are doubled (exact for 16 B/lane streaming reads, an upper estimate for
@@ -52,7 +52,7 @@ def main():
         out[k] = {"launches": max(nf, nw, nv), "read_bytes_per_launch": int(rd), "write_bytes_per_launch": int(wr),
                   "bytes_per_launch": int(rd + wr), "valu_insts_per_launch": int(vi / max(nv, 1))}
     out["_note"] = ("FETCH_SIZE x 1024 x 2 (gfx950 read correction) + WRITE_SIZE x 1024; SQ_INSTS_VALU wave instructions; "
-                    "averaged per launch; three separate --pmc passes of `python3 bench.py --steps 2 --no-cpu --no-also`")
+                    "averaged per launch; three separate --pmc passes of `python3 bench.py --full --steps 2 --no-cpu --no-also`")
     # provenance: bench.py marks these figures stale when the kernel sources it runs are not the ones profiled here
     # provenance = what the PROFILED run loaded (the `build` object of its own JSON line, argv[5] = that run's log), not what
     # the sources look like when this script runs afterwards
@@ -61,7 +61,7 @@ def main():
         for line in open(sys.argv[5]):
             if line.startswith('{"metric"'):
                 stamp = json.loads(line).get("build", stamp)
-    stamp["command"] = "python3 bench.py --steps 2 --no-cpu --no-also --gen-workers 1"
+    stamp["command"] = "python3 bench.py --full --steps 2 --no-cpu --no-also --gen-workers 1"
     stamp["steps_profiled"] = 5  # 2 timed + 2 warm-up + 1 statistics step: what `launches` counts
     out["_stamp"] = stamp
     json.dump(out, open(sys.argv[4], "w"), indent=1, sort_keys=True)

@@ -7,7 +7,7 @@ T=${1:-r4_final}
 O=$R/gpurun_out/$T
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 2 --no-cpu --no-also --gen-workers 1"
+B="python3 $R/bench.py --full --steps 2 --no-cpu --no-also --gen-workers 1"
 for c in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; do
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- $B > $O/pmc_$c.log 2>&1
 done
@@ -26,11 +26,11 @@ cd $R
 python3 tools/dbg/pmc_generic.py $O/pmc_occ > $O/${T}_pmc_occupancy_per_kernel.txt 2>&1
 python3 tools/dbg/pmc_generic.py $O/pmc_l2 > $O/${T}_pmc_l2_per_kernel.txt 2>&1
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace -- python3 $R/bench.py --no-cpu --no-also --gen-workers 1 > $O/ktrace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace -- python3 $R/bench.py --full --no-cpu --no-also --gen-workers 1 > $O/ktrace.log 2>&1
 grep -h "^{\"metric\"" $O/ktrace.log | tail -1 > $O/${T}_bench_under_rocprof.json
 cp $(find $O/ktrace -name "*kernel_stats.csv" | head -1) $O/${T}_kernel_stats.csv
 cd $R
-MA_STREAMS=1 timeout 300 python3 bench.py --no-cpu --no-also 2>/dev/null | tail -1 > $O/${T}_bench_single_lane.json
-if [ "${2:-}" = "full" ]; then timeout 1200 python3 bench.py 2>/dev/null | tail -1 > $O/${T}_bench.json; fi
+MA_STREAMS=1 timeout 300 python3 bench.py --full --no-cpu --no-also 2>/dev/null | tail -1 > $O/${T}_bench_single_lane.json
+if [ "${2:-}" = "full" ]; then timeout 1200 python3 bench.py --full 2>/dev/null | tail -1 > $O/${T}_bench.json; fi
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_SQ_INSTS_VALU $O/pmc_sq $O/pmc_occ $O/pmc_l2 $O/ktrace
 cat $O/${T}_pmc_per_kernel.txt | sort -k5 -n -r | head -30
