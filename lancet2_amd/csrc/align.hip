@@ -39,10 +39,6 @@
 
 #include "ma_internal.h"
 
-// workgroups of the DP kernels in the order heaviest first (0: list order, as until round 6 -- developer A/B builds)
-#ifndef MA_REG_ORDER
-#define MA_REG_ORDER 1
-#endif
 namespace ma {
 
 namespace {
@@ -260,7 +256,7 @@ __device__ PairId pair_decode(GArgs const& A, u64 p) {
   return id;
 }
 
-#if defined(MA_PROFILE) || defined(MA_PROFILE_TRIPS)
+#ifdef MA_PROFILE
 __device__ unsigned long long g_vprof[16];
 #endif
 #ifdef MA_PROFILE
@@ -506,12 +502,6 @@ __device__ __forceinline__ u32 vote_settle(GArgs const& A, u64 lp, PairId id, i3
       }
     }
   }
-#ifdef MA_DP_HIST  // (developer build: how wide are the DP regions?  dp_count[24 ..])
-  if (!(fast_in || fast_ov || nohit)) {
-    u32 const w = static_cast<u32>(vmax - vmin + 2 * Kn + 1);
-    atomicAdd(&A.ws.dp_count[24 + (w <= 5 ? 0 : w <= 9 ? 1 : w <= 13 ? 2 : w <= 17 ? 3 : w <= 25 ? 4 : w <= 33 ? 5 : w <= 41 ? 6 : 7)], 1u);
-  }
-#endif
   i32 const r_lo = vmin - Kn;
   u32 const r_w = static_cast<u32>(vmax - vmin + 2 * Kn + 1);
   // width class of the region; can a row of the kernel's window reach column 0 or n (+ the 7 columns the last
@@ -537,18 +527,12 @@ __device__ __forceinline__ u32 vote_settle(GArgs const& A, u64 lp, PairId id, i3
 __device__ __forceinline__ void vote_pair(GArgs const& A, u64 lp, PairId id, HapIdx ix, u16* hist, int lane, i32 m, u32 pre, i32 hint, i32 n,
                                           bool shortcut_tried);
 
-#ifndef MA_VOTE_PF
-#define MA_VOTE_PF 2
-#endif
 // waves per SIMD the registers are held to (96 VGPRs): five workgroups per CU, as many as their LDS allows -- the
 // kernel spends most of its life waiting for LDS and memory, one more resident workgroup in four is worth 13 % (a sixth,
 // bought with a half-size seed index, costs more in longer bucket chains than it hides)
-#ifndef MA_VOTE_WAVES
-#define MA_VOTE_WAVES 5
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAVES, 8))) void k_vote(GArgs A, u32 hist_len, u32 rwords, u32 ml_eff) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_vote(GArgs A, u32 hist_len, u32 rwords, u32 ml_eff) {
   extern __shared__ u32 lds_vote[];
-#if defined(MA_PROFILE) || defined(MA_PROFILE_TRIPS)
+#ifdef MA_PROFILE
   unsigned long long const k_tstart = __builtin_amdgcn_s_memtime();
 #endif
   u32 const item = A.ws.vote_wg[blockIdx.x];
@@ -703,9 +687,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
     sh_cand[0] = nc;
   }
   __syncthreads();
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP == 1  // (developer timing build, tools/dbg/vote_phases.sh: the set-up alone; results invalid)
-  return;
-#endif
 #ifdef MA_PROFILE
   __shared__ unsigned long long sh_prof[4][8];
   if (lane < 8) sh_prof[wave][lane] = 0;
@@ -722,14 +703,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
   hap_amb = __ballot(hap_amb != 0) ? 1u : 0u;
   HapIdx const ix{head, next, code, hlo, hhi, hbad, rplanes_all + static_cast<size_t>(wave) * 3 * rwords, rwords,
                   dpbuf_all + wave * 129, hap_amb, dup_pre, sh_cand};
-#endif
-#ifdef MA_PROFILE_TRIPS  // (developer build: where a trip of eight reads spends its time -- [0] candidates [1] group vote [2] wave-wide route)
-  unsigned long long const k_t0 = __builtin_amdgcn_s_memtime();
-  if (threadIdx.x == 0) atomicAdd(&g_vprof[15], k_t0 - k_tstart);
-  unsigned long long tp0 = 0, tp1 = 0, tp2 = 0, tp3 = 0, tp4 = 0, tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0;
-#define TRIP_STAMP(v) unsigned long long const v = __builtin_amdgcn_s_memtime()
-#else
-#define TRIP_STAMP(v) do {} while (0)
 #endif
   u16* hist = hist_all + static_cast<size_t>(wave) * hist_len;
   u32 const npw = 3u * rwords;
@@ -777,7 +750,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
       }
       i32 const ncand = ix.cand[0];
       i32 const mmax = static_cast<i32>(sh_mmax);
-      TRIP_STAMP(ts0);
       for (int cx = 0; cx < ncand; ++cx) {
         if (__ballot(can && !settled) == 0ull) break;
         i32 const c = hint - ix.cand[1] + ix.cand[2 + cx];
@@ -834,26 +806,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
           }
         }
       }
-      TRIP_STAMP(ts1);
-      TRIP_STAMP(ts2);
       // the reads that are left go on this wave's list: the wave-wide route runs in a loop of its own below (inlined into this
       // loop it shared the trip's registers: the prefetched words were reloaded from scratch behind a vmcnt(0) every trip)
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP == 2  // (developer timing build: the shortcut trips without the wave-wide route; results invalid)
-      unsigned long long const todo = 0ull;
-#else
       unsigned long long const todo = __ballot(valid && !settled && x == 0);
-#endif
       if ((todo >> lane) & 1ull)
         l_left[nleft + static_cast<u32>(__popcll(todo & ((1ull << lane) - 1ull)))] = static_cast<u16>(ri | (tried ? 0x8000u : 0u));
       nleft += static_cast<u32>(__popcll(todo));
-#ifdef MA_PROFILE_TRIPS
-      tp0 += ts2 - ts0;
-      tp3 += 1;
-#endif
     }
     __builtin_amdgcn_wave_barrier();
   }
-#ifndef MA_NO_GROUP_VOTE
   if (grouped && nleft > 0 && static_cast<i32>(n) >= SK) {
     // ---- the UNANIMOUS vote, eight listed reads side by side (round 5) ---------------------------------------------------
     // What is listed -- reads without a usable hint, with more than two mismatches, with an indel, or hanging far over a
@@ -888,7 +849,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
     u32 nwl, nwh, nwb, nit;
     fetch_item(0, &nwl, &nwh, &nwb, &nit);
     for (u32 q = 0; q < nA; q += 8) {
-      TRIP_STAMP(tg0);
       u32 const wl = nwl, wh = nwh, it = nit;
       u32 bad = nwb;
       fetch_item(q + 8, &nwl, &nwh, &nwb, &nit);  // (the next eight listed reads: in flight under this trip)
@@ -927,11 +887,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
       u32 multi = 0;
       // (the loop is bound by VALU issue -- ~60 instructions per lane and position in its first form, five waves per SIMD:
       //  every load below is unconditional with a harmless address, every update a select, the 64-bit shifts one per batch)
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP == 4  // (developer timing build: the group vote without its lookups; results invalid)
-      i32 const nrun = 0;
-#else
       i32 const nrun = min(pr, np - s);  // this lane's positions: t < nrun (<= 0: none)
-#endif
       for (i32 t0 = 0; t0 < 24; t0 += 8) {
         i32 const nact = nrun - t0;
         if (__ballot(nact > 0) == 0ull) break;
@@ -980,9 +936,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
         // Buckets shared with other 11-mers (one probe in ten): every lane walks ITS pending chains one after the other --
         // a handful of LDS instructions for the wave.  (All eight positions in lock step issued sixteen, mostly empty, per
         // chain step.)
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP == 5  // (developer timing build: first probes only; results invalid)
-        pend = 0;
-#endif
         while (pend != 0) {
           u32 const tt = static_cast<u32>(__builtin_ctz(pend));
           pend &= pend - 1u;
@@ -1007,11 +960,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
         }
       }
       multi &= kCodeDup;
-      TRIP_STAMP(tgA);
       cnt = grp8_sum(cnt);
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP == 6  // (developer timing build: the lookups run, every listed read is then called 'no shared 11-mer'; results invalid)
-      if (cnt != 0x12345678u) cnt = 0;
-#endif
       i32 const lmin = dmin, lmax = dmax;
       dmin = grp8_min(dmin);
       dmax = grp8_max(dmax);
@@ -1073,7 +1022,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
         i32 const g1 = one_gap(xa, xb, c, c2), g2 = one_gap(xb, xa, c2, c);
         if (okc) lb_two = max(g1, g2);
       }
-      TRIP_STAMP(tgB);
       u32 act = kVoteNoHit;
       if ((unan || two) && x == 0) {
         u64 const lp = p - A.pair0;
@@ -1091,10 +1039,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
                             far > 24u ? v2 : 0u, lb_two);
         }
       }
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP == 7  // (developer timing build: the group vote's DP pairs are not queued; results invalid)
-      act = kVoteFast;
-#endif
-      TRIP_STAMP(tgC);
       // the DP pairs of this trip (at most eight) into the wave's buffer: it holds < 64 on entry
       unsigned long long const dpm = __ballot(act < kVoteFast);
       if (dpm != 0ull) {
@@ -1113,37 +1057,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
       }
       // what stays listed (compacted in place: nB <= q, and the entries up to q + 15 have been read)
       unsigned long long const stay = __ballot(valid && !(unan || two) && x == 0);
-#ifdef MA_PROFILE_TRIPS  // (census of what stays listed: a repeat / two or more diagonals without a repeat / not voted here at all)
-      if (lane == 0) {
-        atomicAdd(&g_vprof[9], static_cast<unsigned long long>(__popcll(__ballot(valid && gv && multi != 0 && x == 0))));
-        atomicAdd(&g_vprof[10], static_cast<unsigned long long>(__popcll(__ballot(valid && gv && multi == 0 && !unan && !two && x == 0))));
-        atomicAdd(&g_vprof[11], static_cast<unsigned long long>(__popcll(__ballot(valid && !gv && x == 0))));
-      }
-#endif
       if ((stay >> lane) & 1ull) l_left[nB + static_cast<u32>(__popcll(stay & ((1ull << lane) - 1ull)))] = static_cast<u16>(it & 0xFFFFu);
       nB += static_cast<u32>(__popcll(stay));
-#ifdef MA_PROFILE_TRIPS
-      TRIP_STAMP(tgD);
-      tp1 += tgD - tg0;
-      tq0 += tgA - tg0;
-      tq1 += tgB - tgA;
-      tq2 += tgC - tgB;
-      tq3 += tgD - tgC;
-      tp4 += 1;
-#endif
     }
     __builtin_amdgcn_wave_barrier();
     nleft = nB;
   }
-#endif
-#if defined(MA_VOTE_STOP) && MA_VOTE_STOP >= 3  // (developer timing builds: no wave-wide route after the group vote; results invalid)
-  nleft = 0;
-#endif
   {
     // ---- the wave-wide route: the listed reads (or, without the trips, all of this wave's reads), one after the other ----
     // software pipeline: the next reads' plane words (lane l < 3 rwords holds word l) and mapping hints are in flight while
     // the current read is voted -- kPF reads ahead
-    TRIP_STAMP(tw0);
     u32 const nloop = grouped ? nleft : (nr > static_cast<u32>(wave) ? (nr - static_cast<u32>(wave) + 3u) / 4u : 0u);
     auto item = [&](u32 idx) -> u32 {  // read index, bit 31: the hint shortcut was tried
       if (!grouped) return static_cast<u32>(wave) + 4u * idx;
@@ -1153,7 +1076,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
     auto fetch = [&](u32 ri) -> u32 {
       return static_cast<u32>(lane) < npw ? A.ws.read_planes[static_cast<size_t>(r0 + ri) * plane_stride(rwords) + lane] : 0u;
     };
-    constexpr u32 kPF = MA_VOTE_PF;
+    constexpr u32 kPF = 2;
     u32 pf[kPF], it[kPF];
     i32 hf[kPF];
 #pragma unroll
@@ -1183,10 +1106,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
       hf[kPF - 1] = hn;
       it[kPF - 1] = itn;
     }
-#ifdef MA_PROFILE_TRIPS
-    TRIP_STAMP(tw1);
-    tp2 += tw1 - tw0;
-#endif
   }
   // What the four waves still buffer goes out together: ONE returning atomic per workgroup and one per key present.  (A
   // flush per wave put ~1.5 M atomics per step on the one cache line of dp_count -- each wave's handful of pairs, its
@@ -1211,20 +1130,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA_VOTE_WAV
       if (threadIdx.x < 36 && sh_kh[threadIdx.x] != 0) atomicAdd(&A.ws.dp_count[4 + threadIdx.x], sh_kh[threadIdx.x]);
     }
   }
-#ifdef MA_PROFILE_TRIPS
-  if (lane == 0) {
-    atomicAdd(&g_vprof[0], tp0);
-    atomicAdd(&g_vprof[1], tp1);
-    atomicAdd(&g_vprof[2], tp2);
-    atomicAdd(&g_vprof[7], tp3);
-    atomicAdd(&g_vprof[8], tp4);
-    atomicAdd(&g_vprof[3], tq0);
-    atomicAdd(&g_vprof[4], tq1);
-    atomicAdd(&g_vprof[5], tq2);
-    atomicAdd(&g_vprof[6], tq3);
-    atomicAdd(&g_vprof[14], __builtin_amdgcn_s_memtime() - k_t0);
-  }
-#endif
 #ifdef MA_PROFILE
   __builtin_amdgcn_wave_barrier();
   if (lane < 8) atomicAdd(&g_vprof[lane], sh_prof[wave][lane]);
@@ -1611,7 +1516,7 @@ __device__ __forceinline__ void vote_pair(GArgs const& A, u64 lp, PairId id, Hap
 #endif
 }
 
-#if defined(MA_PROFILE) || defined(MA_PROFILE_TRIPS)
+#ifdef MA_PROFILE
 }  // namespace
 }  // namespace ma
 extern "C" void ma_debug_vprof(unsigned long long* out, int reset) {
@@ -1800,7 +1705,7 @@ __global__ __launch_bounds__(64) void k_align_wave(GArgs A, u32 nchunk_alloc) {
   int const lane = threadIdx.x;
   if (blockIdx.x >= A.dp_n) return;
   // (the class's list is sorted by width step: the widest regions -- the longest workgroups -- start first)
-  u32 const pi = MA_REG_ORDER ? A.dp_n - 1u - blockIdx.x : blockIdx.x;
+  u32 const pi = A.dp_n - 1u - blockIdx.x;
   u64 const lp = A.ws.dp_list[A.dp0 + pi];
   u32 const pr_ = A.ws.pair_read[lp];
   PairId const id{static_cast<int>(A.ws.read_win[pr_ & 0x7FFFFFFu]), pr_ & 0x7FFFFFFu, pr_ >> 27};
@@ -2098,10 +2003,7 @@ __global__ __launch_bounds__(256) void k_dp_scatter(GArgs A, u32 ndp, u32* out, 
 }
 
 // waves per SIMD the register allocator is asked to keep (it otherwise spends registers on scheduling freedom)
-#ifndef MA_RW49
-#define MA_RW49 3
-#endif
-__host__ __device__ constexpr int reg_waves(int w) { return w <= 49 ? MA_RW49 : (w <= 65 ? 3 : (w <= 97 ? 2 : 1)); }
+__host__ __device__ constexpr int reg_waves(int w) { return w <= 65 ? 3 : (w <= 97 ? 2 : 1); }
 // the body of one width class: `group` = the class's 64-pair group this wavefront owns
 template <int W, int WLO>
 __device__ __forceinline__ void align_reg_body(GArgs const& A, u32 seg_words, u32 const group, u32* lds) {
@@ -2265,7 +2167,7 @@ __device__ __forceinline__ void align_reg_body(GArgs const& A, u32 seg_words, u3
 template <int W, int WLO>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(reg_waves(W), 8))) void k_align_reg(GArgs A, u32 seg_words) {
   extern __shared__ u32 lds[];
-  align_reg_body<W, WLO>(A, seg_words, MA_REG_ORDER ? gridDim.x - 1u - blockIdx.x : blockIdx.x, lds);  // (the widest groups first)
+  align_reg_body<W, WLO>(A, seg_words, gridDim.x - 1u - blockIdx.x, lds);  // (the widest groups first)
 }
 
 // Two width classes in one launch (the first n1 workgroups are class 1's groups): a launch lasts its 150 dependent rows
@@ -2538,17 +2440,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void
   static_assert(reg_waves(W1) == reg_waves(W2), "same register budget");
   // the heaviest groups first: the wider class before the narrower, packed groups (128 pairs) before the others, and -- the DP
   // list of a class is sorted by width step -- a segment's last groups before its first: the launch ends with its cheapest
-  // workgroups (MA_REG_ORDER=0 at build time: in list order, as until round 6)
+  // workgroups
   u32 unit = blockIdx.x;
   int sg = 0;
-  if (MA_REG_ORDER) {
+  {
     constexpr int ord[4] = {1, 0, 3, 2};
     int oi = 0;
     while (oi < 3 && unit >= pl.seg[ord[oi]].units) unit -= pl.seg[ord[oi++]].units;
     sg = ord[oi];
     unit = pl.seg[sg].units - 1u - unit;
-  } else {
-    while (sg < 3 && unit >= pl.seg[sg].units) unit -= pl.seg[sg++].units;
   }
   reg_seg_apply(A, pl.seg[sg]);
   if (sg == 0) {
@@ -3196,7 +3096,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     size_t const lds_vote = 4ull * ml_eff + 2ull * kIdxCap + 2ull * ((ml_eff + 1) & ~1) + 8ull * hist_len +
                             12ull * pw_host + 48ull * rwords + 4ull * 4 * 129 + 2ull * (ml_eff + 6) + 2ull * (plan_counters[1] + 4) +
                             8ull * ((plan_counters[1] + 3) / 4 + 10) + 64;
-    if (getenv("MA_VOTE_DEBUG")) fprintf(stderr, "k_vote: %zu B of LDS (ml_eff %u, max reads %u, hist_len %u, rwords %u), %u workgroups\n", lds_vote, ml_eff, plan_counters[1], hist_len, rwords, n_vote_wg);
+    if (getenv("MA_VERBOSE")) fprintf(stderr, "k_vote: %zu B of LDS (ml_eff %u, max reads %u, hist_len %u, rwords %u), %u workgroups\n", lds_vote, ml_eff, plan_counters[1], hist_len, rwords, n_vote_wg);
     if (lds_vote > 65536)
       MA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_vote), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(lds_vote)));
@@ -3213,11 +3113,9 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
       u32 const ndp = cnt[0];
       ctx->stats[1] += ndp;
       if (ndp == 0) continue;
-      if (getenv("MA_VOTE_DEBUG")) {
+      if (getenv("MA_VERBOSE")) {
         fprintf(stderr, "k_vote: %u DP pairs of %u; by (class, wall):", ndp, A.npairs);
         for (int k = 0; k < kNumKeys; ++k) fprintf(stderr, " %u", cnt[4 + k]);
-        fprintf(stderr, "; region widths <= 5 9 13 17 25 33 41 more (MA_DP_HIST builds):");
-        for (int k = 0; k < 8; ++k) fprintf(stderr, " %u", cnt[24 + k]);
         fprintf(stderr, "\n");
       }
       GArgs const Avote = A;
@@ -3273,9 +3171,9 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
         // two register classes of the same register budget, side by side in one launch (k_align_reg2) when both fit the
         // traceback workspace whole
         // (only the classes of at most 49 cells have a paired / packed instantiation: class 3 -- 65 cells -- shares
-        //  reg_waves() == 3 with them when MA_RW49 is 3 and must NOT be taken for one of them)
+        //  reg_waves() == 3 with them and must NOT be taken for one of them)
         auto pair_class = [&](int c) { return c < kNumReg && reg_width(c) <= 49; };
-        if (!wave && pair_class(cls) && !getenv("MA_NO_PAIR")) {
+        if (!wave && pair_class(cls)) {
           int c2 = -1;
           for (int c = cls + 1; c < kNumReg; ++c) {
             if (class_n(c) == 0) continue;

@@ -1,7 +1,6 @@
 // C-ABI entry points of libmicroasm.so (see include/microasm.h).  No CPU fallback: every entry
 // point fails with MA_ERR_NO_DEVICE when there is no HIP device.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -450,21 +449,14 @@ struct CopyOp {
   size_t bytes;
 };
 template <class F>
-int run_copy_ops(ma_ctx* owner, hipStream_t stream, hipStream_t stream2, std::vector<CopyOp> const& ops,
-                 std::vector<size_t> const& group_end, F&& group_done) {
+int run_copy_ops(ma_ctx* owner, hipStream_t stream, std::vector<CopyOp> const& ops, std::vector<size_t> const& group_end,
+                 F&& group_done) {
   // one piece at a time, waited for with a plain stream synchronise (an event or marker behind a DMA copy is a packet on a
-  // compute queue and waits for that queue's turn: 28-33 GB/s instead of 55); MA_UPLOAD_TWO_STREAMS alternates the pieces
-  // between two streams, two in flight (measured: 46.0 instead of 43.2 ms per batch of 8192 windows)
-  static size_t const piece = (getenv("MA_UPLOAD_CHUNK_MB") ? static_cast<size_t>(atoi(getenv("MA_UPLOAD_CHUNK_MB"))) : 16u) << 20;
+  // compute queue and waits for that queue's turn: 28-33 GB/s instead of 55)
+  // (measured: two copy streams with two pieces in flight, 46.0 instead of 43.2 ms per batch of 8192 windows)
+  constexpr size_t piece = size_t(16) << 20;
   auto const t_begin = std::chrono::steady_clock::now();
-  hipStream_t const st[2] = {stream, stream2 ? stream2 : stream};
   size_t queued = 0;
-  static int const dbg_skip = getenv("MA_DEBUG_SKIP_UPLOAD") ? atoi(getenv("MA_DEBUG_SKIP_UPLOAD")) : 0;  // developer experiment:
-  static std::atomic<int> dbg_calls{0};                                                                                // the buffers keep what
-  if (dbg_skip > 0 && ++dbg_calls > dbg_skip) {
-    for (size_t g = 0; g < group_end.size(); ++g) group_done(g);
-    return MA_OK;
-  }                                                // the first uploads put there
   for (CopyOp const& op : ops)  // the pads first: a handful of tiny fills
     if (op.bytes && !op.src) MA_HIP(owner, hipMemsetAsync(op.dst, 0, op.bytes, stream));
   size_t grp = 0;
@@ -472,24 +464,16 @@ int run_copy_ops(ma_ctx* owner, hipStream_t stream, hipStream_t stream2, std::ve
     CopyOp const& op = ops[oi];
     while (grp < group_end.size() && oi == group_end[grp]) {  // a lane's slice is complete: its lane may start
       MA_HIP(owner, hipStreamSynchronize(stream));
-      if (stream2) MA_HIP(owner, hipStreamSynchronize(stream2));
       group_done(grp++);
     }
     if (!op.bytes || !op.src) continue;
     for (size_t o = 0; o < op.bytes; o += piece, ++queued) {
-      hipStream_t const s_ = st[queued & 1];
-      if (queued >= (stream2 ? 2u : 1u)) MA_HIP(owner, hipStreamSynchronize(s_));
-      static int const gap_us = getenv("MA_UPLOAD_GAP_US") ? atoi(getenv("MA_UPLOAD_GAP_US")) : 0;
-      if (gap_us > 0 && queued > 0) {  // (experiment: leave the link idle for a moment between pieces)
-        auto const until = std::chrono::steady_clock::now() + std::chrono::microseconds(gap_us);
-        while (std::chrono::steady_clock::now() < until) {}
-      }
+      if (queued > 0) MA_HIP(owner, hipStreamSynchronize(stream));
       MA_HIP(owner, hipMemcpyAsync(static_cast<char*>(op.dst) + o, static_cast<const char*>(op.src) + o, std::min(piece, op.bytes - o),
-                                   hipMemcpyHostToDevice, s_));
+                                   hipMemcpyHostToDevice, stream));
     }
   }
   MA_HIP(owner, hipStreamSynchronize(stream));
-  if (stream2) MA_HIP(owner, hipStreamSynchronize(stream2));
   while (grp < group_end.size()) group_done(grp++);
   if (getenv("MA_VERBOSE")) {
     size_t total = 0;
@@ -664,7 +648,7 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   } else {
     std::vector<CopyOp> ops;
     MA_TRY_RC(stage_lane_inputs(ch, set, b, w0, w1, &ops, &d));
-    MA_TRY_RC(run_copy_ops(ch, ch->stream, nullptr, ops, std::vector<size_t>(), [](size_t) {}));
+    MA_TRY_RC(run_copy_ops(ch, ch->stream, ops, std::vector<size_t>(), [](size_t) {}));
   }
   // ---- device-side outputs of the lane (fixed strides, as the kernels write them) ----
   LaneOut o;
@@ -876,14 +860,13 @@ void uploader_loop(ma_ctx* ctx, HostAsync* ha) {
     {
       auto run = [&]() -> int {
         MA_HIP(ctx, hipSetDevice(ctx->device));
-        return run_copy_ops(ctx, ctx->copy_stream, getenv("MA_UPLOAD_TWO_STREAMS") ? ctx->copy_stream2 : nullptr, t->ops, t->lane_end,
-                            [&](size_t g) {
-                              {
-                                std::lock_guard<std::mutex> lk(t->mu);
-                                t->lanes_done = g + 1;
-                              }
-                              t->cv.notify_all();
-                            });
+        return run_copy_ops(ctx, ctx->copy_stream, t->ops, t->lane_end, [&](size_t g) {
+          {
+            std::lock_guard<std::mutex> lk(t->mu);
+            t->lanes_done = g + 1;
+          }
+          t->cv.notify_all();
+        });
       };
       rc = run();
     }
@@ -928,14 +911,22 @@ void stop_workers(ma_ctx* ctx) {
   ctx->host_async = nullptr;
 }
 
-int host_lanes(const ma_ctx* ctx, int n_windows) {
-  // the caller's stream carries nothing on this route: the lanes (and the prefetch stream) have the hardware queues to
-  // themselves -- four by default (GPU_MAX_HW_QUEUES), so three lanes + the copy stream unless the host raised it
+// Lanes for a batch of n_windows: the context's own count, else automatic(hwq) -- hwq = the process's hardware queues
+// (GPU_MAX_HW_QUEUES, ROCm's default 4; read once: the variable only means something if it was set before HIP started).
+// MA_STREAMS overrides both; at least two windows per lane, at most 8 lanes.
+template <class F>
+int pick_lanes(const ma_ctx* ctx, int n_windows, F&& automatic) {
   static int const hwq = getenv("GPU_MAX_HW_QUEUES") ? atoi(getenv("GPU_MAX_HW_QUEUES")) : 4;
-  int lanes = ctx->n_lanes > 0 ? ctx->n_lanes : (n_windows >= 2048 ? (hwq >= 6 ? 4 : 3) : (n_windows >= 512 ? 2 : 1));
+  int lanes = ctx->n_lanes > 0 ? ctx->n_lanes : automatic(hwq);
   if (const char* e = getenv("MA_STREAMS")) lanes = atoi(e) > 0 ? atoi(e) : lanes;
   if (lanes > n_windows / 2) lanes = n_windows / 2 > 0 ? n_windows / 2 : 1;
   return lanes > 8 ? 8 : lanes;
+}
+
+int host_lanes(const ma_ctx* ctx, int n_windows) {
+  // the caller's stream carries nothing on this route: the lanes (and the prefetch stream) have the hardware queues to
+  // themselves -- three lanes + the copy stream unless the host raised GPU_MAX_HW_QUEUES
+  return pick_lanes(ctx, n_windows, [&](int hwq) { return n_windows >= 2048 ? (hwq >= 6 ? 4 : 3) : (n_windows >= 512 ? 2 : 1); });
 }
 
 std::vector<int> lane_bounds(int n_windows, int lanes) {
@@ -1121,11 +1112,10 @@ void ma_destroy(ma_ctx_t* ctx) {
     if (pp) (void)hipHostFree(pp);
     pp = nullptr;
   }
-  for (hipStream_t cs : {ctx->copy_stream, ctx->copy_stream2})
-    if (cs) {
-      (void)hipStreamSynchronize(cs);
-      (void)hipStreamDestroy(cs);
-    }
+  if (ctx->copy_stream) {
+    (void)hipStreamSynchronize(ctx->copy_stream);
+    (void)hipStreamDestroy(ctx->copy_stream);
+  }
   for (auto& st : ctx->in_sets)
     for (auto& bf : st.bufs) bf.release();
   for (auto& t : ctx->timers) {
@@ -1364,7 +1354,6 @@ int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
   int const set = !ctx->pf_batch[0] ? 0 : (!ctx->pf_batch[1] ? 1 : -1);
   if (set < 0) return MA_OK;  // two batches are waiting already
   if (!ctx->copy_stream) MA_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  if (!ctx->copy_stream2) MA_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream2, hipStreamNonBlocking));
   int const lanes = host_lanes(ctx, next->n_windows);
   MA_TRY_RC(ensure_workers(ctx, lanes));
   HostAsync* ha = async_of(ctx);
@@ -1400,7 +1389,7 @@ int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
   // ... and its compute jobs behind whatever the lanes are doing: the call that brings the batch will find the records
   // waiting (or on their way).  Not in the statistics-gathering mode of the bench (its device counters are per call).
   ha->jobs[set].reset();
-  if (ha->have_mask && !ctx->collect && !getenv("MA_NO_RUNAHEAD"))
+  if (ha->have_mask && !ctx->collect)
     ha->jobs[set] = submit_host(ctx, lanes, next, set, task, ha->last_mask, nullptr);
   return MA_OK;
 }
@@ -1433,18 +1422,14 @@ int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* ga
   // Automatic: three lanes for big batches -- the process has four hardware queues by default (ROCm's GPU_MAX_HW_QUEUES) and a
   // fourth lane would share one with the caller's stream (measured: -18 %); a host that raises GPU_MAX_HW_QUEUES to >= 6
   // before HIP starts gets four (+2 %).
-  // (read once: the variable only means something if it was set before HIP started)
-  static int const hwq = getenv("GPU_MAX_HW_QUEUES") ? atoi(getenv("GPU_MAX_HW_QUEUES")) : 4;
   // Round 6, since a lane's windows go through every stage in ONE chunk: with a single k (no ladder) TWO lanes of 8192 windows
   // beat four of 4096 (274 against 268 k windows/s on the headline workload; 2 / 3 / 4 / 5 / 6 lanes: 274 / 269 / 268 / 257 /
   // 256) -- every launch has a tail and a latency floor that twice the windows amortise, and two lanes still overlap one
   // stage's tail with another's body.  The ladder's many small rungs want the four (145 against 140 k).
   bool const single_k = ctx->prm.min_k == ctx->prm.max_k;
-  int lanes = ctx->n_lanes > 0 ? ctx->n_lanes
-                               : (d.n_windows >= 8192 && hwq >= 6 ? (single_k ? 2 : 4) : (d.n_windows >= 6144 ? 3 : (d.n_windows >= 2048 ? 2 : 1)));
-  if (const char* e = getenv("MA_STREAMS")) lanes = atoi(e) > 0 ? atoi(e) : lanes;
-  if (lanes > d.n_windows / 2) lanes = d.n_windows / 2 > 0 ? d.n_windows / 2 : 1;
-  if (lanes > 8) lanes = 8;
+  int const lanes = pick_lanes(ctx, d.n_windows, [&](int hwq) {
+    return d.n_windows >= 8192 && hwq >= 6 ? (single_k ? 2 : 4) : (d.n_windows >= 6144 ? 3 : (d.n_windows >= 2048 ? 2 : 1));
+  });
   if (lanes <= 1) {
     MA_TRY(launch_gate(ctx, d, g.dev.max_approx, g.dev.max_exact));
     MA_TRY(launch_assemble(ctx, d, a.dev, g.dev.max_approx));

@@ -237,8 +237,9 @@ __global__ __launch_bounds__(256) void k_spec_select(const SpecDesc* desc, const
 }
 
 constexpr u32 kSpecPendingCap = 2048;
-static u32 const kSpecPending = getenv("MA_SPEC_PENDING") ? static_cast<u32>(atoi(getenv("MA_SPEC_PENDING"))) : 256u;  // windows pending at most
-static u32 const kSpecRungs = getenv("MA_SPEC_RUNGS") ? static_cast<u32>(atoi(getenv("MA_SPEC_RUNGS"))) : 6u;          // rungs per round
+constexpr u32 kSpecPending = 256;  // windows pending at most
+constexpr u32 kSpecRungs = 6;      // rungs per round
+static_assert(kSpecPending <= kSpecPendingCap, "speculation descriptors");
 
 // `active[0, P)` = the pending windows of the chunk, win_k[w] = the rung each of them would attempt next (k_select_active
 // has just run).  Resolves them as far as kSpecRungs rungs go; *still = how many remain pending.
@@ -571,7 +572,7 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
         ws.n_active = static_cast<int>(host_cnt[0]);
         ws.active = active;
         if (host_cnt[1] == 0) break;  // every window of the chunk is resolved (graph.cpp:106 loop exit)
-        if (!nested && kpass >= 1 && ws.n_active > 0 && static_cast<u32>(ws.n_active) <= std::min(kSpecPending, kSpecPendingCap) && P.max_k > P.min_k &&
+        if (!nested && kpass >= 1 && ws.n_active > 0 && static_cast<u32>(ws.n_active) <= kSpecPending && P.max_k > P.min_k &&
             !getenv("MA_NO_SPEC")) {
           // few windows are left on the ladder: their next rungs at once (speculate_tail), until none is pending
           u32 still = 0;
@@ -584,8 +585,8 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
           //  instance bases and the windows' totals are already there.  INVARIANT the skip rests on: the planning
           //  call counted EVERY window at min_k == max_k == this k; seq_inst_base / win_ninst live in the misc carve that no
           //  chunk, capacity-retry pass or k_reset_overflowed writes (those reset node / table / arena state only).  Whoever
-          //  changes win_k handling or moves those arrays must drop the skip; MA_RECOUNT_INST=1 recounts on every pass)
-          if (nested || P.min_k != P.max_k || getenv("MA_RECOUNT_INST")) MA_TRY_RC(run_count_inst(ctx, b, ws, win0, nwin, counters));
+          //  changes win_k handling or moves those arrays must drop the skip)
+          if (nested || P.min_k != P.max_k) MA_TRY_RC(run_count_inst(ctx, b, ws, win0, nwin, counters));
           ws.tc_log2 = tc_log2_alloc;
           ws.mc_log2 = mc_log2_alloc;  // run_build_pass shrinks both to what this attempt needs
           MA_TRY_RC(run_build_pass(ctx, b, ws, counters + 12, tc_log2_alloc));

@@ -56,7 +56,6 @@ struct ChainArgs {
   u32 xe_cap;   // nodes with three or four edges
   u32 seg_cap;  // segments per window (even)
   u32 cl_cap;   // compact nodes the alive list holds (even)
-  u32 stop;     // (developer A/B) leave after phase `stop`: the window then takes the raw route; 0 = run to the end
 };
 
 struct Lds {
@@ -154,7 +153,6 @@ __device__ unsigned long long g_chprof[16];
     unsigned long long const _t1 = __builtin_amdgcn_s_memtime();          \
     if (threadIdx.x == 0) atomicAdd(&g_chprof[slot], _t1 - _t0);          \
     _t0 = _t1;                                                            \
-    if (A.stop == (slot) + 1u) return;                                    \
   } while (0)
 #define CH_SUB0() unsigned long long _s0 = __builtin_amdgcn_s_memtime()
 #define CH_SUB(slot)                                                      \
@@ -165,7 +163,7 @@ __device__ unsigned long long g_chprof[16];
   } while (0)
 #else
 #define CH_T0() do {} while (0)
-#define CH_ACC(slot) do { if (A.stop == (slot) + 1u) return; } while (0)
+#define CH_ACC(slot) do {} while (0)
 #define CH_SUB0() do {} while (0)
 #define CH_SUB(slot) do {} while (0)
 #endif
@@ -1169,8 +1167,7 @@ int run_clean_chains(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_p
   u32 lo = 0;
   for (int l = 0; l < 3; ++l) {
     if (caps[l] <= lo || lds_bytes(caps[l]) > 160 * 1024) continue;
-    ChainArgs args{b, ws, prm, caps[l], lo, xw, caps[l] <= 1472u ? 64u : caps[l] / 8u, caps[l] <= 1472u ? 256u : caps[l] / 4u, caps[l] <= 1472u ? 256u : caps[l] / 4u,
-                   getenv("MA_CHAINS_STOP") ? static_cast<u32>(atoi(getenv("MA_CHAINS_STOP"))) : 0u};
+    ChainArgs args{b, ws, prm, caps[l], lo, xw, caps[l] <= 1472u ? 64u : caps[l] / 8u, caps[l] <= 1472u ? 256u : caps[l] / 4u, caps[l] <= 1472u ? 256u : caps[l] / 4u};
     ctx->tic("k_clean_chains");
     if (l == 0)
       hipLaunchKernelGGL(k_clean_chains, dim3(ws.n_active), dim3(kT), lds_bytes(caps[l]), ctx->stream, args);

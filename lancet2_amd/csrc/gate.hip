@@ -23,9 +23,6 @@ constexpr int kGateFastW = 2560;                 // windows up to here (the refe
 constexpr int kGateCopy = kGateFastW + 64;       // bytes per shifted copy (a multiple of 4)
 constexpr int kGateLds = 4 * kGateCopy;          // >= kGateMaxW + 64: a longer window fits once, unshifted
 
-#ifndef MA_GATE_PACKED
-#define MA_GATE_PACKED 1  // (0: one diagonal per lane everywhere, as until round 6 -- developer A/B builds)
-#endif
 template <int MM>
 __global__ __launch_bounds__(kGateThreads) void gate_kernel(const u8* __restrict__ ref,
                                                             const u32* __restrict__ ref_off, int n_windows,
@@ -60,7 +57,7 @@ __global__ __launch_bounds__(kGateThreads) void gate_kernel(const u8* __restrict
   // the mismatch positions and the two maxima, all below 2^15 -- in the 16-bit halves of one register each (v_pk_sub_i16 /
   // v_pk_max_i16, one v_bfi per state word): 13 vector instructions per position PAIR instead of 2 x 9.5.  Diagonal d + 1 is
   // one position shorter than d: at that one position its half takes no part (`keep`).
-  if (fast && MA_GATE_PACKED) {
+  if (fast) {
     typedef short pk16 __attribute__((ext_vector_type(2)));
     auto as_pk = [](u32 v) { return __builtin_bit_cast(pk16, v); };
     auto as_u = [](pk16 v) { return __builtin_bit_cast(u32, v); };

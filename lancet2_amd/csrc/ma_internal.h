@@ -114,7 +114,6 @@ struct ma_ctx {
   size_t last_packed = 0;                 // (lane) bytes of packed records of the lane's last batch: sizes the next landing area
   void* host_async = nullptr;             // (parent) worker threads + jobs of the host route (api.hip: HostAsync)
   void* dev_pool = nullptr;               // (parent) the lanes' worker threads of the device route (api.hip: DevLanePool)
-  hipStream_t copy_stream2 = nullptr;     // the pieces of an upload alternate between the two copy streams (api.hip: run_copy_ops)
   ma::InputSet in_sets[2];       // (lane) input staging, double buffered
   // (parent) ma_prefetch_batch: which batch each set of the lanes holds (null: free), in which order they were filled,
   // and the stream the uploads of a prefetch run on (api.hip: uploader thread)
@@ -163,7 +162,6 @@ inline int ma_dev_stats(ma_ctx* ctx, unsigned long long** out) {
 // Wait for the context's stream without burning a host core: one process per GPU and up to three lane threads per
 // process would otherwise spin on hipStreamSynchronize (8 GPUs: 24 busy cores for nothing).
 inline hipError_t ma_stream_sync(ma_ctx* ctx) {
-  if (getenv("MA_SPIN_SYNC")) return hipStreamSynchronize(ctx->stream);
   if (!ctx->sync_ev) {
     hipError_t const e = hipEventCreateWithFlags(&ctx->sync_ev, hipEventBlockingSync | hipEventDisableTiming);
     if (e != hipSuccess) return e;

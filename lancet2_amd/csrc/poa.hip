@@ -54,10 +54,7 @@ constexpr i32 kNegInf = static_cast<i32>(0x80000000u) + 1024;
 constexpr i32 M_ = 0, N_ = -6, G_ = -6, E_ = -2, Q_ = -26, C_ = -1;  // msa_builder.h:72-77
 
 // The band tier k_msa can fill on its own wave 0 (tail of a batch, MA_POA_BAND=1); every tier has its k_msa_band.
-#ifndef MA_POA_TIER0
-#define MA_POA_TIER0 2
-#endif
-constexpr u32 kTierIn = MA_POA_TIER0;
+constexpr u32 kTierIn = 2;
 
 constexpr u32 RI_FAST = 1u << 11;     // single predecessor == previous rank
 constexpr u32 RI_SLOWTAB = 1u << 12;  // predecessor rows cached in slowpred[info >> 16]
@@ -72,7 +69,6 @@ struct PoaWs {
   u32 row_slots;     // stored rows per window
   u32 use_band;      // try the banded fills first (see launch_msa: MA_POA_BAND)
   u32 tier0;         // columns per lane of the first band tier: 1 / 2 / 4 = 64 / 128 / 256 columns (MA_POA_TIER0)
-  u32 no_wide_start; // (A/B) every alignment starts at tier0, whatever its length
   u32* tier_stats;   // [8] fills per tier 64/128/256 + (at 4) failed certificates per tier; null unless MA_VERBOSE
   unsigned long long* dstats;  // ma_timing_control mode 3 (else null): [7] band cells, [8] band fills, [9] full-fill cells,
                                // [10] alignments, [11] closed-form alignments (ma_internal.h: dev_stats)
@@ -2261,7 +2257,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
               // the tiers are exact, the result is the same)
               u32 const Lref = A.a.hap_len[static_cast<size_t>(w) * MH + hap0];
               u32 const dl = L > Lref ? L - Lref : Lref - L;
-              u32 const t0 = (ws.tier0 < 4u && dl > 48u && !ws.no_wide_start) ? 4u : ws.tier0;
+              u32 const t0 = (ws.tier0 < 4u && dl > 48u) ? 4u : ws.tier0;
               ST.band = (ws.use_band && L >= 400 && static_cast<size_t>(V + 1) * 256 <= ws.code_cells) ? t0 : 0u;
             }
           }
@@ -3125,6 +3121,7 @@ __global__ __launch_bounds__(64, 4) void k_msa_band(MsaArgs A) {
 // Fresh windows come off one global counter, so the XCDs balance themselves.  A workgroup leaves when no window is left to
 // start and its XCD has more workgroups than open windows.  (MA_POA_XCD=0: one domain for the whole chip, device-scope fences.)
 constexpr u32 kPoaDoms = 16;
+constexpr u32 kPoaMinFills = 16;  // k_poa's policy_min_fills: fills are popped once this many wait
 struct PoaDom {  // one per XCD, a cache line of its own
   u32 f_head, f_tail, g_head, g_tail;
   u32 h_head, h_tail;  // fills of windows that are past their first alignment: taken first (the batch's critical path)
@@ -3386,10 +3383,9 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
 // throughput kernel -- thousands of workgroups queued for every wave slot -- each of their launches waits for slots like
 // everybody else, 29 times per lane-step.  They run on a stream of the greatest priority instead: the dispatcher takes
 // their workgroups first, which costs the throughput kernels a few slots and takes the POA's chain of launches off the
-// step's critical path.  (MA_POA_PRIORITY=0: the lane's own stream, as before.)
+// step's critical path.
 int launch_msa(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o) {
-  static bool const use_hi = !(getenv("MA_POA_PRIORITY") && atoi(getenv("MA_POA_PRIORITY")) == 0);
-  if (!use_hi || b.n_windows == 0) return launch_msa_on_stream(ctx, b, a, o);
+  if (b.n_windows == 0) return launch_msa_on_stream(ctx, b, a, o);
   if (!ctx->hi_stream && !ctx->hi_failed) {  // (a device without stream priorities: the lane's own stream, no error)
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
@@ -3442,7 +3438,7 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
     MA_HIP(ctx, ma_stream_sync(ctx));
   }
   u32 const rounds = std::max<u32>(1u, got[1] + 1u);  // split mode: 1 + the most alignments of any window
-  bool const any_wide = got[2] > 16 && !getenv("MA_POA_NO_LAB32");  // (knob for tests: wide components stay flagged, as in round 5)
+  bool const any_wide = got[2] > 16;
   if (getenv("MA_POA_FORCE_LAB32")) return launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u);  // tests: every window through LAB32
   // The reference has no cap on the haplotypes of a component (cbdg/graph.cpp:846-924, caller/msa_builder.cpp:29-42); the
   // engine's is the caller's max_haps <= 32.  Components of up to 16 haplotypes take the common kernels (16-bit label masks,
@@ -3462,7 +3458,6 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   max_len = std::max<u32>(max_len, 16);
   ws.max_l = max_len;
   u32 pn = max_len + std::max<u32>(256, max_len / 4);
-  if (const char* e = getenv("MA_POA_NODE_CAP")) pn = static_cast<u32>(atoi(e));
   pn = std::min<u32>((pn + 7) & ~7u, 65000);
   // two workgroups per CU when the graph fits in 80 KB of LDS, one otherwise
   while (!lab32 && poa_lds_bytes(pn, max_len, lab32) > 80 * 1024 && pn > max_len + 128) pn -= 8;
@@ -3487,14 +3482,12 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   // first band tier: 64 (1), 128 (2) or 256 (4) columns; a tier whose certificate fails hands over to 256 columns, then
   // to the full fill.  Results do not depend on it (tested).
   {
-    int const t0 = getenv("MA_POA_TIER0") ? atoi(getenv("MA_POA_TIER0")) : MA_POA_TIER0;
+    int const t0 = getenv("MA_POA_TIER0") ? atoi(getenv("MA_POA_TIER0")) : static_cast<int>(kTierIn);
     ws.tier0 = (t0 == 1 || t0 == 2) ? static_cast<u32>(t0) : 4u;
-    ws.no_wide_start = getenv("MA_POA_NO_WIDE_START") ? 1u : 0u;
   }
   // split mode: a band round is launched while at least this many windows wait for a fill; fewer finish inside k_msa
   u32 const min_pending = getenv("MA_POA_MIN_PENDING") ? static_cast<u32>(atoi(getenv("MA_POA_MIN_PENDING"))) : 256u;
   bool const verbose = getenv("MA_VERBOSE") != nullptr;
-  bool const no_retry_rounds = getenv("MA_POA_NO_RETRY_ROUNDS") != nullptr;  // (A/B: round 3's rule)
   ws.img_words = static_cast<u32>((lds + 3) / 4);
   // A window's own areas hold what the band tiers write (at most 256 columns per row: 2.7 MB per window of 1 kb haplotypes);
   // the full fill's whole-row areas (10 MB) belong to whoever runs it -- see PoaWs.
@@ -3586,12 +3579,10 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
       u32 const grid = static_cast<u32>(std::min<size_t>(static_cast<size_t>(nwin), max_workers));
       MA_HIP(ctx, hipMemsetAsync(S, 0, sizeof(PoaSched), ctx->stream));
       MA_HIP(ctx, hipMemsetAsync(fq, 0xFF, 3 * sizeof(u32) * qcap * kPoaDoms, ctx->stream));
-      u32 const min_fills = static_cast<u32>(getenv("MA_POA_MIN_FILLS") ? atoi(getenv("MA_POA_MIN_FILLS")) : 16);
-      static bool const by_work = !(getenv("MA_POA_ORDER") && atoi(getenv("MA_POA_ORDER")) == 0);  // (0: window order, as before)
-      u32* const order = by_work ? hq + static_cast<size_t>(qcap) * kPoaDoms : nullptr;
-      if (order) hipLaunchKernelGGL(k_poa_order, dim3(1), dim3(1024), 0, ctx->stream, args, order, static_cast<u32>(nwin));
+      u32* const order = hq + static_cast<size_t>(qcap) * kPoaDoms;
+      hipLaunchKernelGGL(k_poa_order, dim3(1), dim3(1024), 0, ctx->stream, args, order, static_cast<u32>(nwin));
       ctx->tic("k_poa");
-      hipLaunchKernelGGL(pkern, dim3(grid), dim3(kT), lds, ctx->stream, args, S, fq, gq, hq, qcap, static_cast<u32>(nwin), xcd_local, min_fills,
+      hipLaunchKernelGGL(pkern, dim3(grid), dim3(kT), lds, ctx->stream, args, S, fq, gq, hq, qcap, static_cast<u32>(nwin), xcd_local, kPoaMinFills,
                          static_cast<const u32*>(order));
       ctx->toc();
       if (verbose) {
@@ -3631,7 +3622,7 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
         // failed its certificate: long indels, e.g. the 30-80 base duplications that only assemble further up the k ladder).
         // In-kernel those cost a 256-column fill on one wavefront, or the row-synchronous full fill, per window in turn
         // (12 ms for the slowest window of the ladder workload); a band round costs ~1 ms however few windows it holds.
-        if ((pending < min_pending && (pending_retry == 0 || no_retry_rounds)) || r + 1 >= max_rounds) {
+        if ((pending < min_pending && pending_retry == 0) || r + 1 >= max_rounds) {
           args.round = r + 1;
           args.finish = 1;
           ctx->tic("k_msa");

@@ -1,8 +1,8 @@
 """The PMC figures bench.py prices its kernels with (`roofline.traffic`, `roofline_valu`, `roofline_top5`, `gcups`) come from
 rocprofv3 passes of a separate run: profiles/r6_pmc_per_kernel.json, stamped with a hash of the kernel sources those passes
 were taken on.  Round 5 ended with that file one library behind (`traffic_stale: true` in the driver's line): this test fails
-whenever lancet2_amd/csrc or include/ changed after the committed counters were taken -- re-run
-`gpurun -- bash tools/r6_measure.sh r6_final full` and `bash tools/r6_collect.sh` (tools/, profiles/README.md)."""
+whenever lancet2_amd/csrc or include/ changed after the committed counters were taken -- re-take the set with
+`bash tools/measure_profiles.sh` from the repository root on the GPU machine (profiles/README.md)."""
 import json
 import os
 

@@ -12,6 +12,6 @@ for lib in ${VOTE_LIBS:-libmicroasm.so}; do
   timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \
     --kernel-trace --output-format csv -d $O/pmc_v -- python3 bench.py --steps 1 --warmup 1 --no-cpu --no-also > $O/pmc_v.log 2>&1
   echo "== $lib" >> $O/vote_insts.txt
-  python3 tools/dbg/pmc_generic.py $O/pmc_v "k_vote" >> $O/vote_insts.txt 2>&1
+  python3 tools/pmc_generic.py $O/pmc_v "k_vote" >> $O/vote_insts.txt 2>&1
   rm -rf $O/pmc_v
 done

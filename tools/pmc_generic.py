@@ -1,7 +1,7 @@
 """Developer tool: sums of arbitrary rocprofv3 --pmc counters per kernel name, averaged per launch.
 
-  rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY ... --kernel-trace --output-format csv -d gpurun_out/pmc_x -- python3 bench.py ...
-  python3 tools/dbg/pmc_generic.py gpurun_out/pmc_x [kernel-regex]
+  rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY ... --kernel-trace --output-format csv -d build/pmc_x -- python3 bench.py ...
+  python3 tools/pmc_generic.py build/pmc_x [kernel-regex]
 """
 import csv
 import glob
