@@ -26,6 +26,9 @@ CASES = {
     "c4_indel50": ("C4", 1, 1300, dict(min_k=25, max_k=25), dict(depths=(40, 40))),
     # 18 variants / 5 haplotypes in one window: MaxFlow's walk tree is 2^18 prefixes wide in the reference's search
     "c2_dense_variants": ("C2", 1, 77_009, dict(min_k=25, max_k=25), dict(snv_rate=1e-2, indel_rate=2e-3)),
+    # beyond the 2-bit packing of one word (k <= 32) and of two words (k <= 64); reads with N and soft clips among them
+    "c2_k33": ("C2", 1, 1400, dict(min_k=33, max_k=33), dict(softclip_frac=0.05, n_frac=0.05)),
+    "c2_k65": ("C2", 1, 1500, dict(min_k=65, max_k=65), dict(softclip_frac=0.05, n_frac=0.05)),
 }
 
 

@@ -85,6 +85,9 @@ def test_error_codes_on_bad_arguments():
     bad = capi.default_params(min_k=12, max_k=25)                  # even k
     rc = lib.ma_create(C.byref(bad), 0, 0, C.byref(h))
     assert rc in (-5, -1) and not h.value                         # MA_ERR_PARAM
+    bad = capi.default_params(min_k=25, max_k=257)                 # above the reference's bound (cbdg/graph_params.h:15);
+    rc = lib.ma_create(C.byref(bad), 0, 0, C.byref(h))             # up to 255 is oracle-checked (test_gpu_kmer_sizes.py)
+    assert rc in (-5, -1) and not h.value
     rc = lib.ma_create(C.byref(p), 0, 0, C.byref(h))
     assert rc == 0 and h.value, (rc, h.value)
     try:
