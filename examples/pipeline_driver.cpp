@@ -4,7 +4,7 @@
 //   extract   WindowBuilder tiles the regions; per window the skip gates (N-only, max-k repeat, inactive region), the read
 //             collector (filters, coverage-capped paired downsampling, comparator) and the coverage gate; the windows that
 //             are left are flattened into batches
-//   engine    ma_prefetch_batch(next) + ma_process_batch(this): the next batch uploads under this batch's kernels
+//   engine    ma_prefetch_batch(next) + ma_process_batch(this) (ma_process_stats_batch with --out-vcf): the next batch uploads under this batch's kernels
 //   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
 // Build (no HIP headers needed; zlib only for BAM input):
@@ -40,7 +40,9 @@ struct Outputs {  // caller-owned fixed-stride result buffers of one batch
   std::vector<int32_t> cx_i;
   std::vector<float> cx_f;
   std::vector<double> cx_d;
-  void Allocate(const ma_params_t& p, int n) {
+  ma_fmt_out_t fmt{};  // read-level FORMAT statistics: asked for with --out-vcf only
+  std::vector<double> fmt_d;
+  void Allocate(const ma_params_t& p, int n, bool with_stats) {
     size_t const N = n, MC = p.max_comps, MH = p.max_haps, ML = p.max_hap_len, MR = p.max_runs, MV = p.max_vars, MA = p.max_alts,
                  MP = p.max_allele_bytes, S = p.num_samples;
     size_t const G = (MA + 1) * (MA + 2) / 2;
@@ -74,6 +76,12 @@ struct Outputs {  // caller-owned fixed-stride result buffers of one batch
     vars.allele_pool = tb(N * MP);
     geno.allele_counts = tu(N * MV * S * (MA + 1) * 2); geno.var_qual = td(N * MV);
     geno.var_pl = tu(N * MV * S * G); geno.var_gq = tu(N * MV * S);  // FORMAT PL / GQ (and GT = the smallest PL)
+    if (with_stats) {  // FORMAT NPBQ, CMLOD and BQCD / ASMD / AHDD / HSE (ev_sums is not needed for the VCF)
+      fmt_d.assign(N * MV * S * ((MA + 1) + MA + 4), 0.0);
+      fmt.fmt_npbq = fmt_d.data();
+      fmt.fmt_cmlod = fmt.fmt_npbq + N * MV * S * (MA + 1);
+      fmt.fmt_stat = fmt.fmt_cmlod + N * MV * S * MA;
+    }
   }
 };
 
@@ -511,8 +519,9 @@ int main(int argc, char** argv) {
       if (to_engine.Peek(&nxt)) ma_prefetch_batch(ctx, &nxt->batch->view);  // uploads under this batch's kernels
       auto const t0 = Clock::now();
       j.out = std::make_unique<Outputs>();
-      j.out->Allocate(prm, j.batch->view.n_windows);
-      j.rc = ma_process_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno);
+      j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty());
+      j.rc = ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
+                                    vcf_path.empty() ? nullptr : &j.out->fmt);  // (null: ma_process_batch)
       if (j.rc == MA_OK && !vcf_path.empty())  // INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
         j.rc = ma_annotate_batch(ctx, &j.batch->view, &j.out->asmb, &j.out->vars, gc_frac, &j.out->cx);
       if (j.rc != MA_OK) j.err = ma_last_error(ctx);
@@ -550,7 +559,8 @@ int main(int argc, char** argv) {
       // call can still be replaced by a better covered duplicate from a window that overlaps its own (batches finish in
       // window order here; windows the gates skipped count as done)
       auto const tf = Clock::now();
-      store.AddVariants(RecordsOfBatch(prm, *j.batch, j.out->vars, j.out->geno, as_vcf ? &j.out->cx : nullptr));
+      store.AddVariants(RecordsOfBatch(prm, *j.batch, j.out->vars, j.out->geno, as_vcf ? &j.out->cx : nullptr, true,
+                                       as_vcf ? &j.out->fmt : nullptr, as_vcf ? &j.out->asmb : nullptr));
       size_t const done_upto = j.batch->windows.back().genome_index + 1;
       constexpr size_t kBufferWindows = 100;
       if (done_upto > kBufferWindows && done_upto - kBufferWindows > idx_to_flush) {

@@ -12,6 +12,8 @@
  *   ma_genotype_batch      <- caller::Genotyper::Genotype                 (caller/genotyper.h:219)
  *   ma_annotate_batch      <- core::VariantAnnotator::Annotate{Sequence,Graph}Complexity (core/variant_annotator.h)
  *   ma_process_batch       <- the chained body of ProcessWindow           (core/variant_builder.cpp:229-262)
+ *   ma_genotype_stats_batch / ma_process_stats_batch: the same two calls + seven of the read-level FORMAT statistics
+ *                             (caller/variant_support.h:361-411, caller/variant_call.cpp:141-196, :347-381)
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -28,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MA_VERSION 2
+#define MA_VERSION 3
 
 enum ma_error {
   MA_OK = 0,
@@ -203,6 +205,22 @@ typedef struct ma_cx_out {
                        * (caller::GraphMetrics, variant_annotator.cpp:87-99) */
 } ma_cx_out_t;
 
+/* ---- read-level FORMAT statistics (since MA_VERSION 3) ------------------------------------------------------------ */
+/* One set per (window, variant slot, sample), over the de-duplicated evidence reads that allele_counts counts.  Per evidence
+ * read, from the alignment that won AssignReadToAlleles (genotyper.cpp:269-321): base_qual = the representative base quality
+ * of ComputeLocalScore (local_scorer.cpp:166-279), ref_nm = edit distance to the component's REF haplotype (the read length
+ * without such an alignment, combined_scorer.cpp:24-38), own_nm = edit distance to the winning haplotype, hap_id = that
+ * haplotype's index in its component.  Every member is optional (may be NULL); arrays that are asked for are zero -- fmt_stat
+ * NaN -- in unused variant slots and for samples without evidence. */
+typedef struct ma_fmt_out {
+  uint32_t* ev_sums;   /* [n * max_vars * S * (max_alts+1) * 3] per allele: sum of base_qual, of ref_nm, of own_nm */
+  double* fmt_npbq;    /* [n * max_vars * S * (max_alts+1)] NPBQ: posterior base quality / allele depth
+                        * (caller/posterior_base_qual.cpp:14-40, variant_call.cpp:368-373) */
+  double* fmt_cmlod;   /* [n * max_vars * S * max_alts] CMLOD per ALT (caller/genotype_likelihood.cpp:141-196, :307-345) */
+  double* fmt_stat;    /* [n * max_vars * S * 4] BQCD (base/mann_whitney.h:127-225), ASMD, AHDD (variant_support.h:361-387),
+                        * HSE (variant_support.h:389-411); NaN = missing (the reference's nullopt, "." in the VCF) */
+} ma_fmt_out_t;
+
 typedef struct ma_ctx ma_ctx_t;
 
 int ma_create(const ma_params_t* prm, int device, int memspace, ma_ctx_t** out);
@@ -229,6 +247,14 @@ int ma_annotate_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* as
 int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate,
                      const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno);
 
+/* ma_genotype_batch / ma_process_batch + the read-level FORMAT statistics.  fmt == NULL, or all four members NULL, IS the
+ * plain call: the same kernels, nothing allocated.  Otherwise the genotype stage keeps one 8-byte record per read and
+ * variant slot and one more kernel (k_evid_stats) reduces the evidence reads' records to the statistics. */
+int ma_genotype_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
+                            const ma_geno_out_t* geno, const ma_fmt_out_t* fmt);
+int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
+                           const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt);
+
 /* MA_MEM_HOST only (a no-op otherwise): hand over the batch the caller will pass to ma_process_batch NEXT and return at
  * once -- the staged pipeline of the reference's AsyncWorker (core/async_worker.cpp:47-110: extract window j + 1 while window
  * j is assembled) at batch granularity:
@@ -236,7 +262,7 @@ int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* ga
  * The context uploads the batch in the background (an uploader thread, 16 MB pieces) and queues its COMPUTE behind whatever
  * its lanes are doing: a lane goes from the last kernel of batch j straight to the first of batch j + 1, and
  * ma_process_batch(j + 1) only waits for the packed records and scatters them into the caller's arrays.  Work that was
- * queued ahead assumes that the call will ask for the same optional output arrays as the previous ma_process_batch did, with
+ * queued ahead assumes that the call will ask for the same optional output arrays (statistics included) as the previous one did, with
  * the same parameters and timing mode; if it does not (or asks for the per-read debug taps), the queued results are dropped
  * and the batch is computed in the call -- results never depend on whether, or how, a batch was prefetched.
  * `next` and the arrays it points to must stay unchanged until the ma_process_batch call that consumes it (recognised by

@@ -65,6 +65,10 @@ class GenoOut(C.Structure):
         "allele_counts", "var_qual", "aln_rec", "aln_cigar", "asg_allele", "asg_score", "var_pl", "var_gq")]
 
 
+class FmtOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("ev_sums", "fmt_npbq", "fmt_cmlod", "fmt_stat")]
+
+
 def load_cdll(path=None):
     """dlopen the product library.  PyTorch's ROCm wheels bundle their own HIP runtime (torch/lib/libamdhip64.so, no
     SONAME), libmicroasm.so is linked against the system one: whichever of the two initialises second in a process
@@ -120,6 +124,13 @@ def geno_out_spec(p, n, n_reads, debug=True):
         spec.update(aln_rec=(np.int32, n_reads * MH * 6), aln_cigar=(np.uint32, n_reads * MH * (1 + MCG)),
                     asg_allele=(np.uint8, n_reads * MV), asg_score=(np.float64, n_reads * MV))
     return spec
+
+
+def fmt_out_spec(p, n):
+    """read-level FORMAT statistics (ma_genotype_stats_batch / ma_process_stats_batch); fmt_stat: BQCD, ASMD, AHDD, HSE"""
+    MV, MA, S = p.max_vars, p.max_alts, p.num_samples
+    return dict(ev_sums=(np.uint32, n * MV * S * (MA + 1) * 3), fmt_npbq=(np.float64, n * MV * S * (MA + 1)),
+                fmt_cmlod=(np.float64, n * MV * S * MA), fmt_stat=(np.float64, n * MV * S * 4))
 
 
 def cx_out_spec(p, n):

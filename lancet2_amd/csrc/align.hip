@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "ma_internal.h"
+#include "evidence.h"
 
 namespace ma {
 
@@ -97,6 +98,8 @@ struct AlnWs {
   u64* ev_key;         // [n][ev_cap]
   u32* ev_min;         // [n][ev_cap]
   u8* asg_allele;      // [n_reads * MV] (internal copy when the caller passes NULL)
+  uint2* ev_rec;       // [n_reads * MV] the winning assignment's hap_id, base_qual, own_nm, ref_nm (evidence.h); null unless the
+                       //                call asked for the FORMAT statistics
   // alignment records, COMPACT: one per planned (read, haplotype) pair, indexed by the global pair index
   // pair_off[w] + (rank of the haplotype slot among the window's aligned slots) * reads of the window + read -- the reads of
   // one (window, haplotype) are consecutive, so a wavefront of k_assign (a lane per read) loads 64 records as one run.
@@ -111,6 +114,7 @@ struct GArgs {
   ma_asm_out_t a;
   ma_var_out_t v;
   ma_geno_out_t o;
+  ma_fmt_out_t f;   // read-level FORMAT statistics (all null: off)
   AlnWs ws;
   ma_params_t prm;
   u64 pair0;     // first global pair index of this chunk
@@ -2568,8 +2572,10 @@ struct Scored {
 };
 
 // ScoreReadAtVariant (combined_scorer.cpp:60-108) restricted to the fields that decide the allele
+// kBq: also the representative base quality (*min_bq: the smallest Phred the walk tracks, 255 = none; local_scorer.cpp:166-279)
+template <bool kBq>
 __device__ Scored score_at_variant(Cig cg, i32 score, i32 rs, i32 re, const u8* rb, const u8* rq, u32 rlen,
-                                   const u8* hap, i32 vstart, i32 vlen) {
+                                   const u8* hap, i32 vstart, i32 vlen, u32* min_bq) {
   const f64* phred = reinterpret_cast<const f64*>(c_phred_bits_a);
   const i8* kMatrix = c_score_matrix;
   const u8* target = hap + rs;
@@ -2593,6 +2599,9 @@ __device__ Scored score_at_variant(Cig cg, i32 score, i32 rs, i32 re, const u8* 
           u32 const qp = qpos + static_cast<u32>(y);
           u32 const tp = static_cast<u32>(tpos + y);
           ++aligned;
+          if constexpr (kBq) {
+            if (qp < rlen) *min_bq = min(*min_bq, static_cast<u32>(rq[qp]));
+          }
           if (!(qp >= rlen || tp >= tlen)) {
             u32 const qe = enc_base(rb[qp]), te = enc_base(target[tp]);
             i8 const r = kMatrix[te * 5 + qe];
@@ -2611,6 +2620,9 @@ __device__ Scored score_at_variant(Cig cg, i32 score, i32 rs, i32 re, const u8* 
           for (u32 y = 0; y < len; ++y) {
             ++aligned;
             pbq += 3.0;
+            if constexpr (kBq) {
+              if (qpos + y < rlen) *min_bq = min(*min_bq, static_cast<u32>(rq[qpos + y]));
+            }
           }
         qpos += len;
       } else if (op == 2) {
@@ -2619,6 +2631,10 @@ __device__ Scored score_at_variant(Cig cg, i32 score, i32 rs, i32 re, const u8* 
           pbq += 3.0;
         }
         tpos += static_cast<i32>(len);
+        if constexpr (kBq) {  // the bases on both sides of EVERY deletion the walk reaches, in the region or not (:258-262)
+          if (qpos > 0 && qpos - 1 < rlen) *min_bq = min(*min_bq, static_cast<u32>(rq[qpos - 1]));
+          if (qpos < rlen) *min_bq = min(*min_bq, static_cast<u32>(rq[qpos]));
+        }
       } else if (op == 4) {
         qpos += len;
       }
@@ -2639,11 +2655,6 @@ __device__ Scored score_at_variant(Cig cg, i32 score, i32 rs, i32 re, const u8* 
   s.local_identity = identity;
   s.allele = 0;
   return s;
-}
-
-__device__ __forceinline__ u64 ev_key_of(u32 var, u32 sample, u32 allele, u32 qname) {
-  return ((static_cast<u64>(var) << 44) | (static_cast<u64>(sample) << 40) | (static_cast<u64>(allele) << 33) |
-          (static_cast<u64>(qname) << 1)) + 1ull;
 }
 
 // the caller's debug taps (fixed stride [read][max_haps]; cleared by the launcher): every hit's record copied to its place
@@ -2673,16 +2684,7 @@ __global__ __launch_bounds__(256) void k_tap_records(GArgs A, u64 total_pairs) {
   }
 }
 
-// The evidence table of a window: [ev_cap] slots are reserved for every window (the largest one sizes them), a window uses
-// the first ev_slots() of its own -- a power of two holding 1.5 x (its reads x its variants) keys, every read files at most
-// one key per variant -- and only those are cleared per batch: 1-2 k of the 8 k slots on the whole-genome workload (the two
-// whole-array memsets were 1.6 GB per step of 16384 windows, 2.3 ms of fill kernels).
-__device__ __forceinline__ u32 ev_slots(u32 nrw, u32 nv, u32 cap_max) {
-  u64 const need = static_cast<u64>(nrw) * nv * 3u / 2u + 16u;
-  if (need >= cap_max) return cap_max;
-  u32 const c = 1u << (32 - __builtin_clz(static_cast<u32>(need) - 1u));
-  return min(max(c, 64u), cap_max);
-}
+// (the evidence table's sizing, ev_slots(), is in evidence.h: k_evid_stats probes the same tables)
 __global__ __launch_bounds__(256) void k_ev_clear(GArgs A) {
   int const w = blockIdx.x;
   u32 const nv = A.v.win_nvars[w];
@@ -2695,6 +2697,10 @@ __global__ __launch_bounds__(256) void k_ev_clear(GArgs A) {
 }
 
 // AssignReadToAlleles (genotyper.cpp:269-321): one lane per read
+// kStats: the call asked for the read-level FORMAT statistics -- the winner's hap_id, base_qual, own_nm and the read's ref_nm
+// are kept per (read, variant) for k_evid_stats (evidence.hip); the common path launches k_assign<false>, which is the
+// kernel as it was
+template <bool kStats>
 __global__ __launch_bounds__(64) void k_assign(GArgs A) {
   i64 const r = static_cast<i64>(blockIdx.x) * 64 + threadIdx.x;
   if (r >= A.b.n_reads) return;
@@ -2735,11 +2741,14 @@ __global__ __launch_bounds__(64) void k_assign(GArgs A) {
     size_t const ci = static_cast<size_t>(w) * P.max_comps + c;
     u32 const hap0 = A.a.comp_hap0[ci], nh = A.a.comp_nhaps[ci];
     if (!(mask & (1u << hap0))) continue;
+    u32 ref_nm = rlen;  // combined_scorer.cpp:24-38: NM against the component's REF haplotype, the read length without one
+    bool ref_nm_done = false;
     for (u32 v = 0; v < nv; ++v) {
       size_t const vi = static_cast<size_t>(w) * MV + v;
       if (A.v.var_comp[vi] != c) continue;
       bool have_best = false;
       Scored bestsc{};
+      u32 best_h = 0, best_bq = 255;
       for (u32 h = 0; h < nh; ++h) {  // alignments in haplotype order (all_alns)
         u64 const gp = gp_read + static_cast<u64>(__popc(mask & ((1u << (hap0 + h)) - 1u))) * nrw;
         if (!(mask & (1u << (hap0 + h)))) continue;  // (not aligned: no record)
@@ -2766,13 +2775,38 @@ __global__ __launch_bounds__(64) void k_assign(GArgs A) {
         i32 const rs = static_cast<i32>(ah.y & 0xFFFFu), re = static_cast<i32>(ah.y >> 16);
         if (!((vstart + vlen) > rs && vstart < re)) continue;  // OverlapsAlignment (:360-362)
         const u8* hap = A.a.hap_bases + (static_cast<size_t>(w) * MH + hap0 + h) * P.max_hap_len;
-        Scored sc = score_at_variant(cg, static_cast<i32>(ah.x), rs, re, rb, rq, rlen, hap, vstart, vlen);
+        u32 bq = 255;
+        Scored sc = score_at_variant<kStats>(cg, static_cast<i32>(ah.x), rs, re, rb, rq, rlen, hap, vstart, vlen, &bq);
         sc.allele = allele;
         if (have_best && sc.combined() <= bestsc.combined()) continue;  // first wins ties
         bestsc = sc;
         have_best = true;
+        if constexpr (kStats) {
+          best_h = h;
+          best_bq = bq;
+        }
       }
       if (!have_best) continue;
+      if constexpr (kStats) {
+        auto nm_of = [&](u32 h) -> u32 {  // ComputeEditDistance of the read's alignment to haplotype h (a hit), else the read length
+          u64 const gp = gp_read + static_cast<u64>(__popc(mask & ((1u << (hap0 + h)) - 1u))) * nrw;
+          const u32* rp = rec_at(A.ws, gp);
+          uint4 const ah = *reinterpret_cast<const uint4*>(rp);
+          i32 const rs = static_cast<i32>(ah.y & 0xFFFFu), re = static_cast<i32>(ah.y >> 16);
+          if (!ah.w || rs >= re) return rlen;
+          u32 const nops = ah.w < static_cast<u32>(MCG) ? ah.w : static_cast<u32>(MCG);
+          Cig cg{ah.w <= 4u ? rp + 4 : cig_at(A.ws, A.prm, gp) + 1, nops};
+          const u8* hap = A.a.hap_bases + (static_cast<size_t>(w) * MH + hap0 + h) * P.max_hap_len;
+          return edit_distance(cg, rb, rlen, hap + rs, static_cast<u32>(re - rs));
+        };
+        if (!ref_nm_done) {  // (the same for every variant of the component)
+          ref_nm = nm_of(0);
+          ref_nm_done = true;
+        }
+        // (the winner overlaps the variant, so rs < re: nm_of never answers the read length for it)
+        u32 const own_nm = best_h == 0 ? ref_nm : nm_of(best_h);
+        A.ws.ev_rec[static_cast<size_t>(r) * MV + v] = ev_rec_pack(best_h, best_bq == 255 ? 0u : best_bq, own_nm, ref_nm);
+      }
       asg[v] = static_cast<u8>(bestsc.allele);
       if (A.o.asg_allele) A.o.asg_allele[static_cast<size_t>(r) * MV + v] = static_cast<u8>(bestsc.allele);
       if (A.o.asg_score) A.o.asg_score[static_cast<size_t>(r) * MV + v] = bestsc.combined();
@@ -2965,7 +2999,7 @@ __global__ __launch_bounds__(256) void k_qual(GArgs A) {
 }  // namespace
 
 int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& v,
-                    const ma_geno_out_t& o_in) {
+                    const ma_geno_out_t& o_in, const ma_fmt_out_t* fmt) {
   int const n = b.n_windows;
   if (n == 0) return MA_OK;
   ma_params_t const& P = ctx->prm;
@@ -2980,6 +3014,8 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
   A.a = a;
   A.v = v;
   A.o = o_in;
+  bool const stats = fmt && fmt_wanted(*fmt);
+  if (stats) A.f = *fmt;
   A.prm = P;
   AlnWs& ws = A.ws;
   // evidence table: sized from the largest window (reads x a few variants each); the read count per
@@ -3025,6 +3061,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     ws.ev_key = reinterpret_cast<u64*>(take(8ull * n * ws.ev_cap));
     ws.ev_min = reinterpret_cast<u32*>(take(4ull * n * ws.ev_cap));
     ws.asg_allele = reinterpret_cast<u8*>(take(NR * MV + 16));
+    ws.ev_rec = stats ? reinterpret_cast<uint2*>(take(8ull * NR * MV + 16)) : nullptr;
     return off;
   };
   size_t const fixed = carve_fixed(nullptr);
@@ -3345,7 +3382,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     ctx->toc();
   }
   ctx->tic("k_assign");
-  hipLaunchKernelGGL(k_assign, dim3(static_cast<u32>((NR + 63) / 64)), dim3(64), 0, ctx->stream, A);
+  hipLaunchKernelGGL(stats ? k_assign<true> : k_assign<false>, dim3(static_cast<u32>((NR + 63) / 64)), dim3(64), 0, ctx->stream, A);
   ctx->toc();
   ctx->tic("k_evidence");
   hipLaunchKernelGGL(k_evidence, dim3(static_cast<u32>((NR + 63) / 64)), dim3(64), 0, ctx->stream, A);
@@ -3361,6 +3398,19 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     hipLaunchKernelGGL(kq, dim3(static_cast<u32>((static_cast<size_t>(n) * MV + 255) / 256)), dim3(256), 0, ctx->stream, A);
   }
   ctx->toc();
+  if (stats) {
+    EvStatArgs E{};
+    E.n_windows = n;
+    E.prm = P;
+    E.read_win_off = b.read_win_off; E.read_qname_id = b.read_qname_id; E.read_sample = b.read_sample;
+    E.comp_nhaps = a.comp_nhaps;
+    E.win_nvars = v.win_nvars; E.var_comp = v.var_comp; E.var_nalts = v.var_nalts; E.alt_length = v.alt_length;
+    E.win_slotmask = ws.win_slotmask; E.ev_key = ws.ev_key; E.ev_min = ws.ev_min; E.ev_cap = ws.ev_cap;
+    E.asg_allele = ws.asg_allele; E.ev_rec = ws.ev_rec;
+    E.allele_counts = A.o.allele_counts;
+    E.o = A.f;
+    MA_TRY_RC(launch_evid_stats(ctx, E));
+  }
   MA_HIP(ctx, hipGetLastError());
   return MA_OK;
 }

@@ -14,6 +14,7 @@
 
 #include "ma_internal.h"
 #include "pack.h"
+#include "evidence.h"
 
 using namespace ma;
 
@@ -81,6 +82,12 @@ std::vector<OutField> geno_fields(const ma_params_t& p, int n, i64 nr) {
           {off_of(&ma_geno_out_t::asg_score), 8 * R * MV},
           {off_of(&ma_geno_out_t::var_pl), 4 * N * MV * S * ((MA + 1) * (MA + 2) / 2)},
           {off_of(&ma_geno_out_t::var_gq), 4 * N * MV * S}};
+}
+
+std::vector<OutField> fmt_fields(const ma_params_t& p, int n) {
+  size_t const N = n, MV = p.max_vars, MA = p.max_alts, S = p.num_samples;
+  return {{off_of(&ma_fmt_out_t::ev_sums), 4 * N * MV * S * (MA + 1) * 3}, {off_of(&ma_fmt_out_t::fmt_npbq), 8 * N * MV * S * (MA + 1)},
+          {off_of(&ma_fmt_out_t::fmt_cmlod), 8 * N * MV * S * MA}, {off_of(&ma_fmt_out_t::fmt_stat), 8 * N * MV * S * 4}};
 }
 
 std::vector<OutField> cx_fields(const ma_params_t& p, int n) {
@@ -208,7 +215,7 @@ void advance_fields(S* s, const std::vector<OutField>& per_unit, size_t first, s
 
 // One contiguous window range [w0, w1) of the batch on a child context.  All pointers are device pointers.
 int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, int w0, int w1, u32 r0, u32 r1, ma_gate_out_t g,
-             ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, int lane_index) {
+             ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, ma_fmt_out_t f, int lane_index) {
   MA_HIP(ch, hipSetDevice(ch->device));
   MA_HIP(ch, hipStreamWaitEvent(ch->stream, start, 0));
   (void)lane_index;  // (starting the lanes a few ms apart was measured: every ms of stagger is lost, the lanes do overlap)
@@ -235,10 +242,11 @@ int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, int w0, int w1, u
   advance_fields(&q, gf, 0, 2, w0);   // allele_counts, var_qual: per window
   advance_fields(&q, gf, 2, 6, r0);   // alignment / assignment taps: per read
   advance_fields(&q, gf, 6, 8, w0);   // PL, GQ: per window
+  advance_fields(&f, fmt_fields(p, 1), 0, 99, w0);  // (all null without the statistics)
   MA_TRY_RC(launch_gate(ch, d, g.max_approx, g.max_exact));
   MA_TRY_RC(launch_assemble(ch, d, a, g.max_approx));
   MA_TRY_RC(launch_msa(ch, d, a, v));
-  MA_TRY_RC(launch_genotype(ch, d, a, v, q));
+  MA_TRY_RC(launch_genotype(ch, d, a, v, q, &f));
   MA_HIP(ch, hipEventRecord(ch->lane_done, ch->stream));
   return MA_OK;
 }
@@ -301,7 +309,7 @@ struct DevLanePool {
 };
 
 int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const ma_gate_out_t& g, const ma_asm_out_t& a,
-                     const ma_var_out_t& v, const ma_geno_out_t& q) {
+                     const ma_var_out_t& v, const ma_geno_out_t& q, const ma_fmt_out_t& f) {
   while (static_cast<int>(ctx->lanes.size()) < lanes) {
     ma_ctx* ch = new (std::nothrow) ma_ctx();
     if (!ch) return MA_ERR_NOMEM;
@@ -332,7 +340,7 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const ma_gate_out_
   }
   if (!ctx->dev_pool) ctx->dev_pool = new DevLanePool();
   static_cast<DevLanePool*>(ctx->dev_pool)->run(lanes, [&](int k) {
-    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, k);
+    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, k);
   });
   for (int k = 0; k < lanes; ++k) {
     if (rc[k] != MA_OK) {
@@ -362,6 +370,7 @@ struct LaneOut {
   ma_asm_out_t a{};
   ma_var_out_t v{};
   ma_geno_out_t q{};
+  ma_fmt_out_t f{};
 };
 
 int ensure_pinned(ma_ctx* ch, int set, size_t bytes) {
@@ -388,7 +397,7 @@ int alloc_fields(ma_ctx* ch, S* dev, const std::vector<OutField>& f, size_t stag
   return MA_OK;
 }
 
-// The output arrays of the route, as tables: which struct (0 gate, 1 asm, 2 var, 3 geno) and member, bytes per window.
+// The output arrays of the route, as tables: which struct (0 gate, 1 asm, 2 var, 3 geno, 4 fmt) and member, bytes per window.
 struct DenseDesc { int strct; size_t off; size_t win_bytes; };  // small per-window arrays: copied whole
 struct SegDesc { int strct; size_t off; size_t win_stride, unit; u32 kind; };  // packed: only what a window uses
 std::vector<DenseDesc> dense_table(const ma_params_t& p) {
@@ -418,10 +427,14 @@ std::vector<SegDesc> seg_table(const ma_params_t& p) {
           var(2, off_of(&ma_var_out_t::var_hap_allele), 1, MH), var(2, off_of(&ma_var_out_t::var_hap_start), 4, MH),
           {2, off_of(&ma_var_out_t::allele_pool), MP, 0, PK_POOL},
           var(3, off_of(&ma_geno_out_t::allele_counts), 4, S * (MA_ + 1) * 2), var(3, off_of(&ma_geno_out_t::var_qual), 8, 1),
-          var(3, off_of(&ma_geno_out_t::var_pl), 4, S * G), var(3, off_of(&ma_geno_out_t::var_gq), 4, S)};
+          var(3, off_of(&ma_geno_out_t::var_pl), 4, S * G), var(3, off_of(&ma_geno_out_t::var_gq), 4, S),
+          // entries 19 .. 22: the read-level FORMAT statistics (kSegFmt0: lane_compute's allocation goes by these numbers)
+          var(4, off_of(&ma_fmt_out_t::ev_sums), 4, S * (MA_ + 1) * 3), var(4, off_of(&ma_fmt_out_t::fmt_npbq), 8, S * (MA_ + 1)),
+          var(4, off_of(&ma_fmt_out_t::fmt_cmlod), 8, S * MA_), var(4, off_of(&ma_fmt_out_t::fmt_stat), 8, S * 4)};
 }
-struct OutPtrs {  // the four output structs of a call, by table index
-  const void* s[4];
+constexpr int kSegFmt0 = 19;  // seg_table: first entry of the statistics
+struct OutPtrs {  // the five output structs of a call, by table index (the fifth, the statistics, may be null)
+  const void* s[5];
   void* at(int strct, size_t off) const { return s[strct] ? ptr_at(s[strct], off) : nullptr; }
 };
 // which packed arrays the caller asked for (bit i = entry i of seg_table)
@@ -668,6 +681,10 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     need[6] = (job.mask >> 17) & 1u;  // seg_table: var_pl, var_gq
     need[7] = (job.mask >> 18) & 1u;
     MA_TRY_RC(alloc_fields(ch, &o.q, qf, 32, need));
+    std::vector<OutField> const ff = fmt_fields(p, n);
+    std::vector<bool> need_f(ff.size(), false);  // the statistics the caller asked for (none: nothing is allocated)
+    for (size_t i = 0; i < ff.size(); ++i) need_f[i] = (job.mask >> (kSegFmt0 + i)) & 1u;
+    MA_TRY_RC(alloc_fields(ch, &o.f, ff, 44, need_f));
   }
   t_up = since();
   MA_TRY_RC(launch_gate(ch, d, o.g.max_approx, o.g.max_exact));
@@ -676,10 +693,10 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   t_asm = since();
   MA_TRY_RC(launch_msa(ch, d, o.a, o.v));
   t_msa = since();
-  MA_TRY_RC(launch_genotype(ch, d, o.a, o.v, o.q));
+  MA_TRY_RC(launch_genotype(ch, d, o.a, o.v, o.q, &o.f));
   t_geno = since();
   // ---- results: the small dense arrays whole, the rest as packed records, all into the landing area ----
-  OutPtrs const dev{{&o.g, &o.a, &o.v, &o.q}};
+  OutPtrs const dev{{&o.g, &o.a, &o.v, &o.q, &o.f}};
   size_t const N = n, MH = p.max_haps, MV = p.max_vars, MCG = p.max_cigar;
   std::vector<DenseDesc> const dense = dense_table(p);
   PackArgs D{};
@@ -776,6 +793,10 @@ void lane_deliver(const ma_params_t& p, HostJob const& job, int k, OutPtrs const
   for (size_t i = 0; i < segs.size(); ++i) {
     if (!((job.mask >> i) & 1u)) continue;
     u8* hp = static_cast<u8*>(user.at(segs[i].strct, segs[i].off));  // (non-null: the mask is the caller's)
+    // the statistics promise zeros -- fmt_stat NaNs -- in the variant slots a window does not use: the records only bring
+    // the used ones
+    if (segs[i].strct == 4)
+      std::memset(hp + W0 * segs[i].win_stride, segs[i].off == off_of(&ma_fmt_out_t::fmt_stat) ? 0xFF : 0, N * segs[i].win_stride);
     H.seg[H.nseg++] = PackSeg{hp + W0 * segs[i].win_stride, static_cast<u32>(segs[i].win_stride), static_cast<u32>(segs[i].unit),
                               segs[i].kind};
   }
@@ -982,10 +1003,10 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
 }
 
 int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_gate_out_t* g, const ma_asm_out_t* a,
-                 const ma_var_out_t* v, const ma_geno_out_t* q) {
+                 const ma_var_out_t* v, const ma_geno_out_t* q, const ma_fmt_out_t* f) {
   MA_TRY_RC(ensure_workers(ctx, lanes));
   HostAsync* ha = async_of(ctx);
-  OutPtrs const user{{g, a, v, q}};
+  OutPtrs const user{{g, a, v, q, f}};
   u32 const mask = seg_mask_of(ctx->prm, user);
   bool const taps = wants_taps(q);
   // did ma_prefetch_batch upload this batch?  (the oldest set that holds it); otherwise any set that holds nothing
@@ -1305,8 +1326,8 @@ int ma_msa_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, c
   return MA_OK;
 }
 
-int ma_genotype_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
-                      const ma_geno_out_t* out) {
+int ma_genotype_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
+                            const ma_geno_out_t* out, const ma_fmt_out_t* fmt) {
   MA_BEGIN(ctx);
   if (!out || !asmb || !vars) return MA_ERR_ARG;
   DBatch d;
@@ -1317,14 +1338,22 @@ int ma_genotype_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* as
   MA_TRY(v.prepare(ctx, vars, var_fields(ctx->prm, d.n_windows), 16, true));
   OutMirror<ma_geno_out_t> g;
   MA_TRY(g.prepare(ctx, out, geno_fields(ctx->prm, d.n_windows, d.n_reads), 32, false));
-  MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, g.dev));
+  OutMirror<ma_fmt_out_t> f;  // (fmt null: all members null, the stage without the statistics)
+  MA_TRY(f.prepare(ctx, fmt, fmt_fields(ctx->prm, d.n_windows), 44, false));
+  MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, g.dev, &f.dev));
   MA_TRY(g.download(ctx));
+  MA_TRY(f.download(ctx));
   // win_status may gain MA_W_CIGAR_OVERFLOW / MA_W_READ_OVERFLOW
   if (ctx->memspace == MA_MEM_HOST) {
     MA_HIP(ctx, hipMemcpyAsync(asmb->win_status, a.dev.win_status, 4ull * d.n_windows, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));
   }
   return MA_OK;
+}
+
+int ma_genotype_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
+                      const ma_geno_out_t* out) {
+  return ma_genotype_stats_batch(ctx, b, asmb, vars, out, nullptr);
 }
 
 int ma_annotate_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
@@ -1396,6 +1425,11 @@ int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
 
 int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
                      const ma_var_out_t* vars, const ma_geno_out_t* geno) {
+  return ma_process_stats_batch(ctx, b, gate, asmb, vars, geno, nullptr);
+}
+
+int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
+                           const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt) {
   MA_BEGIN(ctx);
   if (!gate || !asmb || !vars || !geno) return MA_ERR_ARG;
   if (!gate->max_approx || !gate->max_exact || !geno->allele_counts || !geno->var_qual) return MA_ERR_ARG;
@@ -1407,7 +1441,7 @@ int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* ga
     if (!asmb->win_status || !asmb->win_ncomp || !asmb->comp_hap0 || !asmb->comp_nhaps || !asmb->hap_len ||
         !asmb->hap_nruns || !vars->win_nvars)
       return MA_ERR_ARG;
-    return process_host(ctx, host_lanes(ctx, b->n_windows), b, gate, asmb, vars, geno);
+    return process_host(ctx, host_lanes(ctx, b->n_windows), b, gate, asmb, vars, geno, fmt);
   }
   DBatch d;
   MA_TRY(stage_batch(ctx, b, &d));
@@ -1419,6 +1453,8 @@ int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* ga
   MA_TRY(v.prepare(ctx, vars, var_fields(ctx->prm, d.n_windows), 16, false));
   OutMirror<ma_geno_out_t> q;
   MA_TRY(q.prepare(ctx, geno, geno_fields(ctx->prm, d.n_windows, d.n_reads), 32, false));
+  OutMirror<ma_fmt_out_t> f;  // (fmt null: all members null)
+  MA_TRY(f.prepare(ctx, fmt, fmt_fields(ctx->prm, d.n_windows), 44, false));
   // Automatic: three lanes for big batches -- the process has four hardware queues by default (ROCm's GPU_MAX_HW_QUEUES) and a
   // fourth lane would share one with the caller's stream (measured: -18 %); a host that raises GPU_MAX_HW_QUEUES to >= 6
   // before HIP starts gets four (+2 %).
@@ -1434,14 +1470,15 @@ int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* ga
     MA_TRY(launch_gate(ctx, d, g.dev.max_approx, g.dev.max_exact));
     MA_TRY(launch_assemble(ctx, d, a.dev, g.dev.max_approx));
     MA_TRY(launch_msa(ctx, d, a.dev, v.dev));
-    MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, q.dev));
+    MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, q.dev, &f.dev));
   } else {
-    MA_TRY(process_in_lanes(ctx, lanes, d, g.dev, a.dev, v.dev, q.dev));
+    MA_TRY(process_in_lanes(ctx, lanes, d, g.dev, a.dev, v.dev, q.dev, f.dev));
   }
   MA_TRY(g.download(ctx));
   MA_TRY(a.download(ctx));
   MA_TRY(v.download(ctx));
   MA_TRY(q.download(ctx));
+  MA_TRY(f.download(ctx));
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
   return MA_OK;
 }

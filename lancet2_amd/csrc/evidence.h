@@ -1,0 +1,60 @@
+// Read-level FORMAT statistics of the genotype stage (evidence.hip): what it shares with align.hip -- the evidence table's
+// key and sizing, the per-read record k_assign<true> leaves for k_evid_stats, and the launch.
+#pragma once
+#include "ma_internal.h"
+
+namespace ma {
+
+__device__ __forceinline__ u64 ev_key_of(u32 var, u32 sample, u32 allele, u32 qname) {
+  return ((static_cast<u64>(var) << 44) | (static_cast<u64>(sample) << 40) | (static_cast<u64>(allele) << 33) |
+          (static_cast<u64>(qname) << 1)) + 1ull;
+}
+
+// The evidence table of a window: [ev_cap] slots are reserved for every window (the largest one sizes them), a window uses
+// the first ev_slots() of its own -- a power of two holding 1.5 x (its reads x its variants) keys, every read files at most
+// one key per variant -- and only those are cleared per batch: 1-2 k of the 8 k slots on the whole-genome workload (the two
+// whole-array memsets were 1.6 GB per step of 16384 windows, 2.3 ms of fill kernels).
+__device__ __forceinline__ u32 ev_slots(u32 nrw, u32 nv, u32 cap_max) {
+  u64 const need = static_cast<u64>(nrw) * nv * 3u / 2u + 16u;
+  if (need >= cap_max) return cap_max;
+  u32 const c = 1u << (32 - __builtin_clz(static_cast<u32>(need) - 1u));
+  return min(max(c, 64u), cap_max);
+}
+
+// The winning assignment of a read at a variant, beside its allele (asg_allele): 8 bytes per (read, variant slot), written by
+// k_assign<true> for the assigned pairs only and read by k_evid_stats for the evidence reads only.
+//   x: hap_id (haplotype within its component, 0 = REF) | base_qual << 8      y: own_nm | ref_nm << 16
+// (a read has at most 608 bases: every edit distance fits 16 bits)
+__device__ __forceinline__ uint2 ev_rec_pack(u32 hap_id, u32 base_qual, u32 own_nm, u32 ref_nm) {
+  return make_uint2(hap_id | (base_qual << 8), min(own_nm, 0xFFFFu) | (min(ref_nm, 0xFFFFu) << 16));
+}
+
+inline bool fmt_wanted(const ma_fmt_out_t& f) { return f.ev_sums || f.fmt_npbq || f.fmt_cmlod || f.fmt_stat; }
+
+struct EvStatArgs {
+  int n_windows;
+  ma_params_t prm;
+  // the batch and the stages before
+  const u32* read_win_off;
+  const u32* read_qname_id;
+  const u8* read_sample;
+  const u32* comp_nhaps;
+  const u32* win_nvars;
+  const u32* var_comp;
+  const u32* var_nalts;
+  const i32* alt_length;
+  // the genotype stage's own
+  const u32* win_slotmask;
+  const u64* ev_key;
+  const u32* ev_min;
+  u32 ev_cap;
+  const u8* asg_allele;     // [n_reads * max_vars]
+  const uint2* ev_rec;      // [n_reads * max_vars]
+  const u32* allele_counts;
+  ma_fmt_out_t o;
+};
+
+// clears the requested arrays (0; fmt_stat: NaN) and launches k_evid_stats on the context's stream
+int launch_evid_stats(ma_ctx* ctx, const EvStatArgs& A);
+
+}  // namespace ma

@@ -198,8 +198,9 @@ struct DBatch {
 int launch_gate(ma_ctx* ctx, const DBatch& b, u32* max_approx, u32* max_exact);
 int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& o, const u32* gate_approx);
 int launch_msa(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o);
+// fmt: the read-level FORMAT statistics (evidence.hip); null, or all members null, is the stage without them
 int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& v,
-                    const ma_geno_out_t& o);
+                    const ma_geno_out_t& o, const ma_fmt_out_t* fmt = nullptr);
 int launch_annotate(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& v, double gc_frac,
                     const ma_cx_out_t& o);
 

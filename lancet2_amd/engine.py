@@ -33,6 +33,8 @@ def load_library(path=None):
     lib.ma_msa_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ma_genotype_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ma_process_batch.argtypes = [C.c_void_p] * 6
+    lib.ma_genotype_stats_batch.argtypes = [C.c_void_p] * 6
+    lib.ma_process_stats_batch.argtypes = [C.c_void_p] * 7
     lib.ma_prefetch_batch.argtypes = [C.c_void_p, C.c_void_p]
     lib.ma_annotate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.ma_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
@@ -136,6 +138,20 @@ class Engine:
                     "ma_genotype_batch")
         return out
 
+    def genotype_stats(self, arrs, n, nr, asm, var, debug=False, fields=None):
+        """ma_genotype_stats_batch: genotype() + the read-level FORMAT statistics (capi.fmt_out_spec; `fields`: a subset of
+        its arrays, default all).  Returns (geno, fmt)."""
+        out = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))
+        fmt = self._alloc({k: s for k, s in capi.fmt_out_spec(self.p, n).items() if fields is None or k in fields})
+        b = capi.make_batch_struct(arrs, n, nr)
+        a = capi.fill_struct(capi.AsmOut, asm)
+        v = capi.fill_struct(capi.VarOut, var)
+        o = capi.fill_struct(capi.GenoOut, out)
+        f = capi.fill_struct(capi.FmtOut, fmt)
+        self._check(self.lib.ma_genotype_stats_batch(self.h, C.byref(b), C.byref(a), C.byref(v), C.byref(o), C.byref(f)),
+                    "ma_genotype_stats_batch")
+        return out, fmt
+
     def annotate(self, arrs, n, nr, asm, var, gc_frac=0.41):
         """VariantAnnotator (core/variant_annotator.cpp:43-101): SEQ_CX + GRAPH_CX of every variant."""
         out = self._alloc(capi.cx_out_spec(self.p, n))
@@ -159,10 +175,29 @@ class Engine:
                                               C.byref(capi.fill_struct(capi.GenoOut, q))), "ma_process_batch")
         return g, a, v, q
 
+    def process_stats(self, arrs, n, nr, debug=False, fields=None):
+        """ma_process_stats_batch: process() + the read-level FORMAT statistics.  Returns (gate, asm, var, geno, fmt)."""
+        g = self._alloc(capi.gate_out_spec(n))
+        a = self._alloc(capi.asm_out_spec(self.p, n))
+        v = self._alloc(capi.var_out_spec(self.p, n))
+        q = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))
+        f = self._alloc({k: s for k, s in capi.fmt_out_spec(self.p, n).items() if fields is None or k in fields})
+        b = capi.make_batch_struct(arrs, n, nr)
+        self._check(self.lib.ma_process_stats_batch(self.h, C.byref(b), C.byref(capi.fill_struct(capi.GateOut, g)),
+                                                    C.byref(capi.fill_struct(capi.AsmOut, a)),
+                                                    C.byref(capi.fill_struct(capi.VarOut, v)),
+                                                    C.byref(capi.fill_struct(capi.GenoOut, q)),
+                                                    C.byref(capi.fill_struct(capi.FmtOut, f))), "ma_process_stats_batch")
+        return g, a, v, q, f
+
     # ---- device-resident path (MA_MEM_DEVICE): dicts of torch tensors (or raw int pointers) ----
     def process_device(self, batch_struct, gate, asm, var, geno):
         self._check(self.lib.ma_process_batch(self.h, C.byref(batch_struct), C.byref(gate), C.byref(asm),
                                               C.byref(var), C.byref(geno)), "ma_process_batch")
+
+    def process_stats_device(self, batch_struct, gate, asm, var, geno, fmt):
+        self._check(self.lib.ma_process_stats_batch(self.h, C.byref(batch_struct), C.byref(gate), C.byref(asm),
+                                                    C.byref(var), C.byref(geno), C.byref(fmt)), "ma_process_stats_batch")
 
     def prefetch(self, batch_struct):
         """MA_MEM_HOST: start uploading the batch that the next process_device() call will be given (ma_prefetch_batch)."""

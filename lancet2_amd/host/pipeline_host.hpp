@@ -22,6 +22,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <optional>
@@ -1243,6 +1244,10 @@ struct VariantRecord {
   std::vector<uint32_t> gq;                         // [sample]
   std::vector<double> sample_window_cov;            // [sample] sampled bases / window length (SDFC's denominator)
   std::string seq_cx, graph_cx;                     // INFO values as the reference formats them (empty: not annotated)
+  // the read-level FORMAT statistics of ma_process_stats_batch (empty: not computed; NaN: missing, "." in the VCF)
+  std::vector<std::vector<double>> npbq, cmlod;     // [sample][allele], [sample][ALT]
+  std::vector<std::array<double, 4>> fmt_stat;      // [sample] BQCD, ASMD, AHDD, HSE
+  double pdcv = std::numeric_limits<double>::quiet_NaN();  // MaxAltPathCv of the variant's component (NaN: none)
   uint64_t TotalCoverage() const {
     uint64_t t = 0;
     for (auto const& s : ad)
@@ -1319,9 +1324,12 @@ class VariantStore {
 };
 
 // ---- VCF text (caller/variant_call.cpp:100-520, caller/sample_format_data.cpp:32-98, cli/vcf_header_builder.cpp:28-63) -------
-// The record layout, INFO field and the FORMAT key are the reference's.  Of the 24 FORMAT values the engine's outputs give
-// GT, AD, ADF, ADR, DP, SB, SDFC, PRAD, PANG, PL and GQ; the read-level statistics (RMQ, NPBQ, SCA, FLD, RPCD, BQCD, MQCD, ASMD,
-// CMLOD, FSSE, AHDD, HSE, PDCV) need per-read data the reference keeps in VariantSupport and are written as missing (".").
+// The record layout, INFO field and the FORMAT key are the reference's.  Of the 24 FORMAT values the engine's outputs give 18:
+// GT, AD, ADF, ADR, DP, SB, SDFC, PRAD, PANG, PL and GQ from the allele depths, NPBQ, BQCD, ASMD, CMLOD, AHDD and HSE from
+// ma_process_stats_batch (RecordsOfBatch's `fmt`) and PDCV from the assembly's comp_cxf.  RMQ, MQCD, SCA, FLD and FSSE need
+// MAPQ, insert size, alignment start, clip and pair flags the batch does not carry, RPCD a per-call sort of f64 values: those
+// six are written as missing (".").  Values pass through f32 where the reference stores f32 (sample_format_data.cpp:32-98,
+// variant_call.cpp:368-373).
 inline constexpr const char* kVcfFormatKey =
     "GT:AD:ADF:ADR:DP:RMQ:NPBQ:SB:SCA:FLD:RPCD:BQCD:MQCD:ASMD:SDFC:PRAD:PANG:CMLOD:FSSE:AHDD:HSE:PDCV:PL:GQ";
 inline double PolarRadius(double ref_depth, double alt_depth) {  // base/polar_coords.h:149-151
@@ -1461,9 +1469,26 @@ inline std::string AsVcfRecord(VariantRecord const& r, Reference const& ref, std
       std::snprintf(sbuf, sizeof sbuf, "%.3f", static_cast<double>(static_cast<float>(std::log((rf1 * ar1) / (rr1 * af1)))));
       sb = sbuf;
     }
+    // the read-level statistics: a number, or "." for a value that is missing (NaN) or was not computed
+    auto num = [](double x, const char* spec, bool via_f32) {
+      if (std::isnan(x)) return std::string(".");
+      char nb[64];
+      std::snprintf(nb, sizeof nb, spec, via_f32 ? static_cast<double>(static_cast<float>(x)) : x);
+      return std::string(nb);
+    };
+    auto list = [&](std::vector<std::vector<double>> const& per_sample, const char* spec, bool via_f32) {
+      if (s >= per_sample.size() || per_sample[s].empty()) return std::string(".");
+      std::string t;
+      for (size_t i = 0; i < per_sample[s].size(); ++i) t += (i ? "," : "") + num(per_sample[s][i], spec, via_f32);
+      return t;
+    };
+    double const kNan = std::numeric_limits<double>::quiet_NaN();
+    std::array<double, 4> const st = s < r.fmt_stat.size() ? r.fmt_stat[s] : std::array<double, 4>{kNan, kNan, kNan, kNan};
     line += "\t" + gt + ":" + join(r.ad[s]) + ":" + (s < r.adf.size() ? join(r.adf[s]) : ".") + ":" +
-            (s < r.adr.size() ? join(r.adr[s]) : ".") + ":" + std::to_string(dp) + ":.:.:" + sb + ":.:.:.:.:.:.:" + sdfc + ":" + polar +
-            ":.:.:.:.:.:" + pl + ":" + (s < r.gq.size() ? std::to_string(r.gq[s]) : ".");
+            (s < r.adr.size() ? join(r.adr[s]) : ".") + ":" + std::to_string(dp) + ":.:" + list(r.npbq, "%.1F", true) + ":" + sb +
+            ":.:.:.:" + num(st[0], "%.4f", true) + ":.:" + num(st[1], "%.3f", true) + ":" + sdfc + ":" + polar + ":" +
+            list(r.cmlod, "%.4F", false) + ":.:" + num(st[2], "%.3f", true) + ":" + num(st[3], "%.4f", true) + ":" +
+            num(r.pdcv, "%.4f", true) + ":" + pl + ":" + (s < r.gq.size() ? std::to_string(r.gq[s]) : ".");
   }
   return line;
 }
@@ -1474,7 +1499,8 @@ inline std::string AsVcfRecord(VariantRecord const& r, Reference const& ref, std
 // from the overlapping window by having more total coverage, and the flush would then drop both.  `supported_only = false`
 // returns every record (tests; callers that want the raw per-window table).
 inline std::vector<VariantRecord> RecordsOfBatch(const ma_params_t& p, FlatBatch const& fb, const ma_var_out_t& v, const ma_geno_out_t& q,
-                                                 const ma_cx_out_t* cx = nullptr, bool supported_only = true) {
+                                                 const ma_cx_out_t* cx = nullptr, bool supported_only = true,
+                                                 const ma_fmt_out_t* fmt = nullptr, const ma_asm_out_t* asmb = nullptr) {
   std::vector<VariantRecord> out;
   int const MV = p.max_vars, MA = p.max_alts, S = p.num_samples, NA = MA + 1;
   for (size_t w = 0; w < fb.windows.size(); ++w) {
@@ -1505,6 +1531,16 @@ inline std::vector<VariantRecord> RecordsOfBatch(const ma_params_t& p, FlatBatch
           r.pl.emplace_back(pl, pl + K * (K + 1) / 2);
         }
         if (q.var_gq) r.gq.push_back(q.var_gq[vi * S + s]);
+        if (fmt) {  // the read-level statistics of this (variant, sample)
+          size_t const cell = vi * S + s;
+          if (fmt->fmt_npbq) r.npbq.emplace_back(fmt->fmt_npbq + cell * NA, fmt->fmt_npbq + cell * NA + K);
+          if (fmt->fmt_cmlod) r.cmlod.emplace_back(fmt->fmt_cmlod + cell * MA, fmt->fmt_cmlod + cell * MA + (K - 1));
+          if (fmt->fmt_stat) r.fmt_stat.push_back({fmt->fmt_stat[cell * 4], fmt->fmt_stat[cell * 4 + 1], fmt->fmt_stat[cell * 4 + 2], fmt->fmt_stat[cell * 4 + 3]});
+        }
+      }
+      if (asmb && asmb->comp_cxf) {  // PDCV: MaxAltPathCv of the variant's component, -1 = no ALT path
+        double const cv = asmb->comp_cxf[(w * static_cast<size_t>(p.max_comps) + v.var_comp[vi]) * 4 + 3];
+        if (cv >= 0.0) r.pdcv = cv;
       }
       for (uint32_t a = 0; a < v.var_nalts[vi]; ++a) {
         r.alt_type.push_back(v.alt_type[vi * MA + a]);

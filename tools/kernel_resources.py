@@ -21,7 +21,7 @@ for src in sorted(glob.glob(os.path.join(R, "lancet2_amd", "csrc", "*.hip"))):
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
             name = re.sub(r"\(anonymous namespace\)::", "", name)
             name = re.sub(r"^void ", "", name).replace("ma::", "")
-            name = re.sub(r"\((GArgs|MsaArgs|CleanArgs|ChainArgs|CxArgs|DBatch|GraphWs|ma_asm_out|unsigned|RegClass2|KeyBase)[^)]*\)$", "", name)
+            name = re.sub(r"\((GArgs|EvStatArgs|MsaArgs|CleanArgs|ChainArgs|CxArgs|DBatch|GraphWs|ma_asm_out|unsigned|RegClass2|KeyBase)[^)]*\)$", "", name)
             cur = {"file": os.path.basename(src), "kernel": name[:72]}
             rows.append(cur)
             continue
