@@ -1187,14 +1187,39 @@ __global__ __launch_bounds__(kSupT) void k_support(DBatch b, GraphWs ws, u32* ma
     }
   }
   __syncthreads();
+  // (sequence sa, sb of this window in one group: same_group() on the cached records)
+  auto same_group_c = [&](u32 sa, u32 sb) {
+    u32 const ma_ = c_meta[sa], mb = c_meta[sb];
+    return (mb & MA_RF_PASS) && c_qn[sa] == c_qn[sb] && ((ma_ ^ mb) & MA_RF_CASE) == 0 && ((ma_ ^ mb) & 0xFF00u) == 0;
+  };
+  // The set-up passes below read a sequence's flags, name and sample from the cached records as well (they loaded the three
+  // arrays from HBM four times over, every load with a wait of its own); a window that is not cached keeps the HBM form.
+  auto same_group_w = [&](u32 sa, u32 sb) {
+    u32 const r0_ = b.read_win_off[w] - 1;
+    return cached ? same_group_c(sa, sb) : same_group(b, r0_ + sa, r0_ + sb);
+  };
+  auto read_rec = [&](u32 sx, u32& fl, u32& qn, u32& sm) {
+    if (cached) {
+      u32 const mt = c_meta[sx];
+      fl = mt & 7u;
+      qn = c_qn[sx];
+      sm = (mt >> 8) & 0xFFu;
+    } else {
+      u32 const r = b.read_win_off[w] + sx - 1;
+      fl = b.read_flags[r];
+      qn = b.read_qname_id[r];
+      sm = b.read_sample[r];
+    }
+  };
   bool const hints = b.read_hint != nullptr && rsi.len <= ws.max_ref_len + 8;
   // (X) every (qname, role) key must belong to ONE sample and to ONE run of adjacent reads; otherwise the
   //     adjacent-group shortcut is not the whole story and every group goes through the general set.
   if (hints) {
     for (u32 s_idx = 1 + threadIdx.x; s_idx < ns; s_idx += kSupT) {
-      u32 const r = b.read_win_off[w] + s_idx - 1;
-      if (!(b.read_flags[r] & MA_RF_PASS)) continue;
-      u32 const key = ((b.read_qname_id[r] << 1) | ((b.read_flags[r] & MA_RF_CASE) ? 1u : 0u)) + 1u;
+      u32 fl, qn, sm;
+      read_rec(s_idx, fl, qn, sm);
+      if (!(fl & MA_RF_PASS)) continue;
+      u32 const key = ((qn << 1) | ((fl & MA_RF_CASE) ? 1u : 0u)) + 1u;
       u32 h = (key * 2654435761u) >> xs_shift;
       bool done = false;
       for (u32 probe = 0; probe < xs_cap && !done; ++probe) {
@@ -1202,7 +1227,7 @@ __global__ __launch_bounds__(kSupT) void k_support(DBatch b, GraphWs ws, u32* ma
         if (cur == 0) {
           u32 const old = atomicCAS(&l_xkey[h], 0u, key);
           if (old == 0) {
-            l_xsmp[h] = b.read_sample[r];
+            l_xsmp[h] = static_cast<u8>(sm);
             done = true;
             break;
           }
@@ -1216,15 +1241,16 @@ __global__ __launch_bounds__(kSupT) void k_support(DBatch b, GraphWs ws, u32* ma
   __syncthreads();
   if (hints) {
     for (u32 s_idx = 1 + threadIdx.x; s_idx < ns; s_idx += kSupT) {
-      u32 const r = b.read_win_off[w] + s_idx - 1;
-      if (!(b.read_flags[r] & MA_RF_PASS)) continue;
-      bool const leader = !(s_idx > 1 && same_group(b, r, r - 1));
-      u32 const key = ((b.read_qname_id[r] << 1) | ((b.read_flags[r] & MA_RF_CASE) ? 1u : 0u)) + 1u;
+      u32 fl, qn, sm;
+      read_rec(s_idx, fl, qn, sm);
+      if (!(fl & MA_RF_PASS)) continue;
+      bool const leader = !(s_idx > 1 && same_group_w(s_idx, s_idx - 1));
+      u32 const key = ((qn << 1) | ((fl & MA_RF_CASE) ? 1u : 0u)) + 1u;
       u32 h = (key * 2654435761u) >> xs_shift;
       for (u32 probe = 0; probe < xs_cap; ++probe) {
         u32 const cur = l_xkey[h];
         if (cur == key) {
-          if (l_xsmp[h] != b.read_sample[r]) xs_flag = 1;
+          if (l_xsmp[h] != sm) xs_flag = 1;
           if (leader && atomicAdd(&l_xgrp[h], 1u) != 0) xs_flag = 1;  // same name in two separate runs
           break;
         }
@@ -1244,14 +1270,16 @@ __global__ __launch_bounds__(kSupT) void k_support(DBatch b, GraphWs ws, u32* ma
     }
   }
   __syncthreads();
-  bool const all_generic = !hints || xs_flag != 0;
+  // (wave-uniform, and known to the compiler as such: the conditions on them in the group loop are scalar branches)
+  auto const uni = [](u32 v) { return static_cast<u32>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); };
+  bool const all_generic = uni((!hints || xs_flag != 0) ? 1u : 0u) != 0;
   // Round 5, QUEUE MODE (every window whose (qname, role) keys are runs of adjacent reads and whose sequences fit an 11-bit
   // leader index -- all but deep panels and windows without hints): a general instance's mate-mer KEY (table slot << 11 |
   // run leader) is appended to the window's queue right here, where its word is in a register anyway; k_mm_q builds the LDS set
   // from the queue.  k_mm_lds found the general instances by streaming all of the window's instance words again (311 KB per
   // window for 31 KB of keys) and needed a GEN bit written back into each of them (a scattered 4-byte store per instance).
   // The queue is the slow queue's memory: k_insert is done with it.
-  bool const qmode = !all_generic && !ws.mm_force_hbm && ns <= kSeqCap && tbl_log2(ws) <= 20;
+  bool const qmode = uni((!all_generic && !ws.mm_force_hbm && ns <= kSeqCap && tbl_log2(ws) <= 20) ? 1u : 0u) != 0;
   u32* const genq = ws.slowq + static_cast<size_t>(a) * ws.inst_stride;
   // DEDUP MODE.  A key names its run's leader, and a run is one group of mates -- handled by ONE wavefront, right here.  So
   // the set over the window's keys is a union of per-group sets, and a group's set (its reads' general instances, a few
@@ -1274,31 +1302,211 @@ __global__ __launch_bounds__(kSupT) void k_support(DBatch b, GraphWs ws, u32* ma
   // leaders of the groups, in any order (counting commutes)
   u32* const l_leaders = l_mask;  // [max_reads + 2] (the per-thread masks of the old mapping lived here)
   if (threadIdx.x == 0) n_leaders = 0;
+  // The window's ref_slot row (the table slot of a reference position: what a FAST general instance is queued under) as u16
+  // in the memory of check (X)'s key and group tables, which nobody reads from here on: the fast route of the group loop
+  // then issues no load from HBM after its instance words.  A table of at most 2^16 slots -- every window k_graph takes.
+  u16* const l_rs = reinterpret_cast<u16*>(l_xkey);
+  bool const rs_lds = uni((cached && tbl_log2(ws) <= 16 && ws.ref_stride <= 4u * xs_cap) ? 1u : 0u) != 0;
+  if (rs_lds)
+    for (u32 i = threadIdx.x; i < ws.ref_stride; i += kSupT) l_rs[i] = i < rsi.nk ? static_cast<u16>(ref_slot_g[i]) : u16(0);
   __syncthreads();
   for (u32 s_idx = 1 + threadIdx.x; s_idx < ns; s_idx += kSupT) {
-    u32 const r0 = b.read_win_off[w] + s_idx - 1;
-    if (!(b.read_flags[r0] & MA_RF_PASS)) continue;
-    if (s_idx > 1 && same_group(b, r0, r0 - 1)) continue;  // not the leader
+    u32 fl, qn, sm;
+    read_rec(s_idx, fl, qn, sm);
+    if (!(fl & MA_RF_PASS)) continue;
+    if (s_idx > 1 && same_group_w(s_idx, s_idx - 1)) continue;  // not the leader
     l_leaders[atomicAdd(&n_leaders, 1u)] = s_idx;
-    if (qmode) {  // k-mers of the whole group against the dedup table's capacity (3/4 full at most)
+    if (qmode) {  // k-mers of the whole group against the dedup table's capacity (3/4 full at most; a cached count of
+                  // 0xFFFF stands for that many or more: above every table's capacity either way)
       u32 tot = 0;
-      for (u32 j = 0; s_idx + j < ns && (j == 0 || same_group(b, r0, r0 + j)); ++j) tot += seq_info(b, w, s_idx + j, k).nk;
+      for (u32 j = 0; s_idx + j < ns && (j == 0 || same_group_w(s_idx, s_idx + j)); ++j)
+        tot += cached ? c_meta[s_idx + j] >> 16 : seq_info(b, w, s_idx + j, k).nk;
       if (tot > dd_cap / 4u * 3u) any_big = 1;
     }
   }
   __syncthreads();
-  bool const qdedup = qmode && ws.graph_fused && !any_big && ws.win_nslots[a] <= kGrSlots;
+  bool const qdedup = uni((qmode && ws.graph_fused && !any_big && ws.win_nslots[a] <= kGrSlots) ? 1u : 0u) != 0;
   IPROF_T0();
-  u32 const wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  u32 const wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  u32 const ns_u = uni(ns), n_lead = uni(n_leaders);
+  // lanes below this one among the set bits of a ballot
+  auto const below = [](unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi(static_cast<u32>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<u32>(m), 0u));
+  };
+  auto const same_rec = [](u32 ma_, u32 qa, u32 mb, u32 qb) {
+    return (mb & MA_RF_PASS) && qa == qb && ((ma_ ^ mb) & MA_RF_CASE) == 0 && ((ma_ ^ mb) & 0xFF00u) == 0;
+  };
   u32* const dd = l_dd + (wave << ws.dd_log2);
   u32 wave_gen = 0;
-  // (sequence sa, sb of this window in one group: same_group() on the cached records)
-  auto same_group_c = [&](u32 sa, u32 sb) {
-    u32 const ma_ = c_meta[sa], mb = c_meta[sb];
-    return (mb & MA_RF_PASS) && c_qn[sa] == c_qn[sb] && ((ma_ ^ mb) & MA_RF_CASE) == 0 && ((ma_ ^ mb) & 0xFF00u) == 0;
+  // (the group led by s_idx: its first two records and its size -- 3 stands for more than two; true if the fast route takes it)
+  auto const fast_group = [&](u32 s_idx, u32& mta, u32& mtb, u32& fsize) {
+    mta = uni(c_meta[s_idx]);
+    mtb = 0;
+    fsize = 1;
+    if (s_idx + 1 < ns_u) {
+      u32 const qa = uni(c_qn[s_idx]);
+      mtb = uni(c_meta[s_idx + 1]);
+      if (same_rec(mta, qa, mtb, uni(c_qn[s_idx + 1]))) {
+        fsize = 2;
+        if (s_idx + 2 < ns_u && same_rec(mta, qa, uni(c_meta[s_idx + 2]), uni(c_qn[s_idx + 2]))) fsize = 3;
+      }
+    }
+    return fsize <= 2 && (mta >> 16) <= 128u && (fsize < 2 || (mtb >> 16) <= 128u);
   };
-  for (u32 gi = wave; gi < n_leaders; gi += kSupT / 64) {
-    u32 const s_idx = l_leaders[gi];
+  u32 n_general = rs_lds ? 0u : 1u;  // groups left to the general loop
+  if (rs_lds) {
+  for (u32 gi = wave; gi < n_lead; gi += kSupT / 64) {
+    u32 const s_idx = uni(l_leaders[gi]);
+    // FAST ROUTE: a group of one or two mates of at most 128 k-mers each with cached records (every ordinary group).  All of
+    // the group's state is scalar; its up to four vectors of instance words are loaded at once and waited for once, and
+    // nothing is loaded from HBM after that.  The trips are classified first -- edges, general instances, the first mate's
+    // counted offsets, the second mate's duplicates are functions of the words and the scalar state --, then the group takes
+    // ONE place in the edge queue and one in the general queue, stores and counts: the stores are never waited for inside a
+    // group.  (The loop below waits for all memory at every trip of 64 k-mers, its own queue stores included.)  The route
+    // has a loop of its own: in one loop with the general route, whose loads may be in flight at the loop's head, the
+    // compiler waits for all memory before each of the four loads.
+    {
+      u32 mta, mtb, fsize;
+      if (!fast_group(s_idx, mta, mtb, fsize)) {
+        ++n_general;
+        continue;
+      }
+      u32 const nka = mta >> 16, nkb = fsize == 2 ? mtb >> 16 : 0u;
+      {
+        bool const generic = all_generic || (((mta | (fsize == 2 ? mtb : 0u)) & 8u) != 0);
+        u32 const iba = uni(c_ib[s_idx]), ibb = fsize == 2 ? uni(c_ib[s_idx + 1]) : 0u;
+        i32 const hint0 = hints ? static_cast<i32>(uni(static_cast<u32>(c_hint[s_idx]))) : 0;
+        // (mates of one group have one sample and one role: same_group)
+        u32 const smp = min((mta >> 8) & 0xFFu, static_cast<u32>(S) - 1u), role = (mta & MA_RF_CASE) ? 1u : 0u;
+        u32 wd[4], nx[4];
+        wd[0] = lane < nka ? inst_slot[iba + lane] : 0u;
+        wd[1] = 64u + lane < nka ? inst_slot[iba + 64u + lane] : 0u;
+        wd[2] = lane < nkb ? inst_slot[ibb + lane] : 0u;
+        wd[3] = 64u + lane < nkb ? inst_slot[ibb + 64u + lane] : 0u;
+        // the group's one wait for memory: all four vectors are used here, so none is still in flight on any path below
+        asm volatile("" ::"v"(wd[0]), "v"(wd[1]), "v"(wd[2]), "v"(wd[3]));
+        // classify: em = (k+1)-mers for the edge queue, gk = general instances, ck = FAST instances to count
+        unsigned long long em[4], gk[4], ck[4], m0a = 0, m0b = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          u32 const nkg = j < 2 ? nka : nkb, ob = (j & 1) * 64u;
+          em[j] = gk[j] = ck[j] = 0;
+          nx[j] = 0;
+          if (ob >= nkg) continue;
+          u32 const o = ob + lane, word = wd[j];
+          u32 const first_next = (j & 1) ? 0u : uni(wd[j | 1]);  // the word at offset 64 (the neighbour of lane 63's)
+          u32 const dn = __shfl_down(word, 1, 64);
+          u32 const nextw = lane == 63 ? first_next : dn;
+          nx[j] = nextw;
+          bool const pair = o + 1 < nkg && !((word & kInstFast) && (nextw & kInstFast) &&
+                                             (nextw & kInstSlotMask) == (word & kInstSlotMask) + 1u);
+          em[j] = __ballot(pair);
+          bool const ef = (word & kInstErrFree) != 0;
+          bool const to_gen = ef && (generic || !(word & kInstFast));
+          gk[j] = __ballot(to_gen);
+          bool const fast = ef && !to_gen;
+          bool dup = false;
+          if (j < 2) {  // offsets of the first mate that are counted
+            if (j == 0) m0a = __ballot(fast); else m0b = __ballot(fast);
+          } else if (fast) {  // did the first mate count this reference position?
+            i64 const o0 = static_cast<i64>(word & kInstSlotMask) - hint0;
+            if (o0 >= 0 && o0 < static_cast<i64>(nka)) dup = (((o0 >> 6) ? m0b : m0a) >> (o0 & 63)) & 1ull;
+          }
+          ck[j] = __ballot(fast && !dup);
+        }
+        // emit: edge queue
+        u32 const ne = static_cast<u32>(__popcll(em[0]) + __popcll(em[1]) + __popcll(em[2]) + __popcll(em[3]));
+        if (ne) {
+          u32 eb = 0;
+          if (lane == 0) eb = atomicAdd(&edgeq_n, ne);
+          eb = uni(eb);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if ((em[j] >> lane) & 1ull)
+              edgeq[eb + below(em[j])] = edge_pack((j < 2 ? iba : ibb) + (j & 1) * 64u + lane, wd[j], nx[j]);
+            eb += static_cast<u32>(__popcll(em[j]));
+          }
+        }
+        // emit: general instances
+        u32 const ng = static_cast<u32>(__popcll(gk[0]) + __popcll(gk[1]) + __popcll(gk[2]) + __popcll(gk[3]));
+        if (ng) {
+          wave_gen += ng;
+          if (qmode) {
+            u32 nsl[4];
+            unsigned long long qk[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              qk[j] = 0;
+              nsl[j] = 0;
+              if (!gk[j]) continue;
+              bool const to_gen = (gk[j] >> lane) & 1ull;
+              u32 const p = wd[j] & kInstSlotMask;
+              u32 const nslot = to_gen ? ((wd[j] & kInstFast) ? static_cast<u32>(l_rs[p]) : p) : 0u;
+              nsl[j] = nslot;
+              if (qdedup) {
+                bool won = false;
+                if (to_gen) {  // first of its (table slot, group)?  (as in the loop below)
+                  u32 const tag = gi + 1u, mine = (nslot << 11) | tag;
+                  u32 h = (nslot * 2654435761u) >> (32u - ws.dd_log2);
+                  for (;;) {
+                    u32 cur = dd[h];
+                    if ((cur & 0x7FFu) != tag) {
+                      u32 const old = atomicCAS(&dd[h], cur, mine);
+                      if (old == cur) {
+                        won = true;
+                        break;
+                      }
+                      cur = old;
+                      if ((cur & 0x7FFu) != tag) continue;
+                    }
+                    if (cur == mine) break;  // counted already
+                    h = (h + 1u) & (dd_cap - 1u);
+                  }
+                }
+                qk[j] = __ballot(won);
+              } else {
+                qk[j] = gk[j];
+              }
+            }
+            u32 const nq = static_cast<u32>(__popcll(qk[0]) + __popcll(qk[1]) + __popcll(qk[2]) + __popcll(qk[3]));
+            if (nq) {
+              u32 qb = 0;
+              if (lane == 0) qb = atomicAdd(&genq_n, nq);
+              qb = uni(qb);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                if ((qk[j] >> lane) & 1ull)
+                  genq[qb + below(qk[j])] = qdedup ? ((nsl[j] << 4) | (smp << 1) | role) : (((nsl[j] << 11) | (s_idx - 1u)) + 1u);
+                qb += static_cast<u32>(__popcll(qk[j]));
+              }
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if ((gk[j] >> lane) & 1ull)  // exact handling by the mate-mer set kernels
+                inst_slot[(j < 2 ? iba : ibb) + (j & 1) * 64u + lane] = wd[j] | kInstGen;
+          }
+        }
+        // count
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if ((ck[j] >> lane) & 1ull) {
+            u32 const p = wd[j] & kInstSlotMask;
+            u32 const i1 = p * CW + smp, i2 = p * CW + S + role;
+            atomicAdd(&l_cnt[i1 >> 1], 1u << ((i1 & 1u) * 16u));
+            atomicAdd(&l_cnt[i2 >> 1], 1u << ((i2 & 1u) * 16u));
+          }
+        }
+      }
+    }
+  }
+  }
+  for (u32 gi = wave; n_general != 0 && gi < n_lead; gi += kSupT / 64) {
+    u32 const s_idx = uni(l_leaders[gi]);
+    if (rs_lds) {
+      u32 mta, mtb, fsize;
+      if (fast_group(s_idx, mta, mtb, fsize)) continue;
+    }
     u32 const r0 = b.read_win_off[w] + s_idx - 1;
     u32 gsize = 1;
     if (cached) {
@@ -2768,6 +2976,8 @@ int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev,
     }
     fprintf(stderr, "[ma] mate-mer sets: %zu windows, %zu need the HBM set (%zu by size), mean general instances %.0f, max %u / %u; pool %.1f of %.1f MB\n",
             A, nfb, big, static_cast<double>(tot) / static_cast<double>(A), max_gen[0], max_gen[1], used / 1048576.0, ws.mm_pool_bytes / 1048576.0);
+    fprintf(stderr, "[ma] k_support: %zu bytes of LDS per workgroup (ref_stride %u, max_reads %u, cache %u, xs_log2 %u)\n", lds_s,
+            ws.ref_stride, ws.max_reads, sup_cache, xs_log2);
   }
   // node records + edges: k_graph for the common window (table of at most 8192 slots), the three general kernels for the rest
   MA_HIP(ctx, hipMemsetAsync(ws.gr_done, 0, 4 * A, ctx->stream));
