@@ -5,6 +5,7 @@
 //             collector (filters, coverage-capped paired downsampling, comparator) and the coverage gate; the windows that
 //             are left are flattened into batches
 //   engine    ma_prefetch_batch(next) + ma_process_batch(this) (ma_process_stats_batch with --out-vcf): the next batch uploads under this batch's kernels
+//             (--packed-reads: the ma_*_packed_batch pair on 4-bit read bases and qualities, half the bytes over the link)
 //   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
 // Build (no HIP headers needed; zlib only for BAM input):
@@ -145,6 +146,7 @@ void DumpBatch(const std::string& dir, FlatBatch const& fb) {
   put("read_off.u64", fb.read_off.data(), 8 * fb.read_off.size());
   put("read_bases.u8", fb.read_bases.data(), fb.read_bases.size());
   put("read_quals.u8", fb.read_quals.data(), fb.read_quals.size());
+  if (fb.packed_mode) put("bases4.u8", fb.bases4.data(), fb.bases4.size());  // (--packed-reads: read_bases.u8 is the pad alone)
   put("read_qname_id.u32", fb.read_qname_id.data(), 4 * fb.read_qname_id.size());
   put("read_sample.u8", fb.read_sample.data(), fb.read_sample.size());
   put("read_flags.u8", fb.read_flags.data(), fb.read_flags.size());
@@ -159,7 +161,7 @@ void DumpBatch(const std::string& dir, FlatBatch const& fb) {
   put("windows.u64", wins.data(), 8 * wins.size());
 }
 
-AlignmentSource LoadAlignments(const std::string& path, Reference const& ref) {
+AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed) {
   bool const bam = path.size() > 4 && path.substr(path.size() - 4) == ".bam";
 #ifdef LANCET2_AMD_WITH_ZLIB
   if (bam) {
@@ -167,9 +169,9 @@ AlignmentSource LoadAlignments(const std::string& path, Reference const& ref) {
     // without one the whole file is read once
     for (std::string const& bai : {path + ".bai", path.substr(0, path.size() - 4) + ".bai"}) {
       std::ifstream probe(bai, std::ios::binary);
-      if (probe && !getenv("PIPELINE_NO_INDEX")) return AlignmentSource::OpenIndexedBam(path, bai, ref);
+      if (probe && !getenv("PIPELINE_NO_INDEX")) return AlignmentSource::OpenIndexedBam(path, bai, ref, keep_packed);
     }
-    return AlignmentSource::LoadBam(path, ref);
+    return AlignmentSource::LoadBam(path, ref, keep_packed);
   }
 #else
   if (bam) throw std::runtime_error("built without zlib (-DLANCET2_AMD_WITH_ZLIB -lz): BAM input is not available");
@@ -197,7 +199,7 @@ int main(int argc, char** argv) {
   ReadCollector::Params rp;
   ma_params_t prm;
   ma_default_params(&prm);
-  bool no_active_region = false, extract_only = false, collect_reads = false;
+  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false;
   int batch_windows = 512;
   int extract_threads = static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
   for (int i = 1; i < argc; ++i) {
@@ -226,19 +228,29 @@ int main(int argc, char** argv) {
     else if (a == "--extract-threads") extract_threads = std::max(1, std::atoi(next()));  // (the reference: -T, one collector per worker)
     else if (a == "--dump") dump_dir = next();
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
+    else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
     else if (a == "--extract-only") extract_only = true;  // stage 1 alone (with --dump): no device needed
     else { std::fprintf(stderr, "pipeline_driver: unknown option %s\n", a.c_str()); return 2; }
   }
   if (ref_path.empty() || (normals.empty() && tumors.empty())) {
-    std::fprintf(stderr, "usage: pipeline_driver --reference ref.fa [--normal n.sam|bam]... [--tumor t.sam|bam]... [--region chr:a-b]... [--out calls.tsv]\n");
+    std::fprintf(stderr, "usage: pipeline_driver --reference ref.fa [--normal n.sam|bam]... [--tumor t.sam|bam]... [--region chr:a-b]... [--out calls.tsv]\n"
+                         "  --packed-reads  read bases (and <= 16 distinct qualities per batch) go to the engine as 4-bit codes: a BAM record's\n"
+                         "                  sequence bytes are copied undecoded, SAM text is packed.  A base letter that is none of BAM's\n"
+                         "                  =ACMGRSVTWYHKDBN (lower case included) becomes N, as in a BAM file; without the flag it is passed on\n"
+                         "                  as it is.  Not with --collect-reads / --extract-pairs\n");
     return 2;
   }
+  if (packed_reads && (collect_reads || rp.extract_pairs)) {
+    std::fprintf(stderr, "pipeline_driver: --packed-reads needs the flat collector (not with --collect-reads / --extract-pairs)\n");
+    return 2;
+  }
+  rp.packed_reads = packed_reads;
   Reference const ref = Reference::LoadFasta(ref_path);
   std::vector<AlignmentSource> sources;
   sources.reserve(normals.size() + tumors.size());
   std::vector<SampleInfo> samples;
   auto add_sample = [&](const std::string& path, Tag tag) {
-    sources.push_back(LoadAlignments(path, ref));
+    sources.push_back(LoadAlignments(path, ref, packed_reads));  // (packed: BAM records keep their sequence bytes)
     std::string name = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
     name = name.substr(0, name.find_last_of('.'));
     samples.push_back({name, tag, nullptr, 0, 0, 0});
@@ -419,6 +431,7 @@ int main(int argc, char** argv) {
         }
       }
       if (!j.batch) j.batch = std::make_unique<FlatBatch>();
+      j.batch->packed_mode = packed_reads;
       if (hint_reads) j.batch->Reserve(static_cast<size_t>(batch_windows), hint_ref, hint_reads, hint_bases);
       return j;
     };
@@ -444,6 +457,7 @@ int main(int argc, char** argv) {
         Job j = std::move(pending.front().job);
         pending.pop_front();
         j.batch->Seal();
+        if (packed_reads) j.batch->PackReads();
         busy_extract += secs(Clock::now() - ts);  // (the Push below may wait for the engine: not this stage's time)
         if (!dump_dir.empty()) {
           char sub[64];
@@ -460,7 +474,7 @@ int main(int argc, char** argv) {
       if (cur.batch->windows.empty()) return;
       auto const ts = Clock::now();
       cur.batch->SizeForPlaced();
-      hint_bases = cur.batch->read_bases.size() + cur.batch->read_bases.size() / 16;
+      hint_bases = cur.batch->read_quals.size() + cur.batch->read_quals.size() / 16;
       hint_reads = cur.batch->read_qname_id.size() + cur.batch->read_qname_id.size() / 16;
       hint_ref = cur.batch->ref_bases.size() + 64;
       auto left = std::make_unique<std::atomic<size_t>>(staged.size());
@@ -516,12 +530,17 @@ int main(int argc, char** argv) {
         continue;
       }
       Job* nxt = nullptr;
-      if (to_engine.Peek(&nxt)) ma_prefetch_batch(ctx, &nxt->batch->view);  // uploads under this batch's kernels
+      if (to_engine.Peek(&nxt)) {  // uploads under this batch's kernels
+        if (packed_reads) ma_prefetch_packed_batch(ctx, &nxt->batch->packed_view, &nxt->batch->packed);
+        else ma_prefetch_batch(ctx, &nxt->batch->view);
+      }
       auto const t0 = Clock::now();
       j.out = std::make_unique<Outputs>();
       j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty());
-      j.rc = ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
-                                    vcf_path.empty() ? nullptr : &j.out->fmt);  // (null: ma_process_batch)
+      const ma_fmt_out_t* fmt = vcf_path.empty() ? nullptr : &j.out->fmt;  // (null: ma_process_batch)
+      j.rc = packed_reads ? ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb,
+                                                    &j.out->vars, &j.out->geno, fmt)
+                          : ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, fmt);
       if (j.rc == MA_OK && !vcf_path.empty())  // INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
         j.rc = ma_annotate_batch(ctx, &j.batch->view, &j.out->asmb, &j.out->vars, gc_frac, &j.out->cx);
       if (j.rc != MA_OK) j.err = ma_last_error(ctx);

@@ -14,6 +14,8 @@
  *   ma_process_batch       <- the chained body of ProcessWindow           (core/variant_builder.cpp:229-262)
  *   ma_genotype_stats_batch / ma_process_stats_batch: the same two calls + seven of the read-level FORMAT statistics
  *                             (caller/variant_support.h:361-411, caller/variant_call.cpp:141-196, :347-381)
+ *   ma_process_packed_batch / ma_prefetch_packed_batch: ma_process_stats_batch / ma_prefetch_batch with the read bases, and
+ *                             optionally the qualities, as 4-bit codes (ma_packed_reads_t): half the bytes over the link
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -221,6 +223,26 @@ typedef struct ma_fmt_out {
                         * HSE (variant_support.h:389-411); NaN = missing (the reference's nullopt, "." in the VCF) */
 } ma_fmt_out_t;
 
+/* ---- packed read input: 4-bit bases, 4- or 8-bit qualities -------------------------------------------------------- */
+/* The read bases -- and, when the batch holds at most 16 distinct Phred values, the qualities -- of a batch as 4-bit codes:
+ * what BAM stores and binned instruments emit, and half of what ma_batch_t::read_bases / read_quals put on the link.  The
+ * library expands them on the device (one kernel, k_unpack_reads) into the very ASCII and Phred arrays the stages read from a
+ * plain call, so results are those of the plain call on the decoded arrays, byte for byte.
+ *
+ * A nibble array holds read after read, high nibble first.  Read r starts on a BYTE boundary, at byte (read_off[r] + r) >> 1,
+ * and occupies (len + 1) / 2 bytes; the low nibble of the last byte of an odd-length read is ignored.  The whole array is
+ * (read_off[n_reads] + n_reads + 1) / 2 bytes long.  The rule needs no offsets of its own and reads never overlap
+ * (floor((x + len + 1) / 2) - floor(x / 2) >= ceil(len / 2)); bytes between two reads are ignored.  A host can memcpy the
+ * sequence bytes of a BAM record straight to the read's offset: the base codes are BAM's.  (The kernel reads the aligned
+ * 4-byte words that hold a byte of the array, nothing beyond them.) */
+typedef struct ma_packed_reads {
+  const uint8_t* bases4;   /* 4-bit base codes, BAM's own: index into "=ACMGRSVTWYHKDBN", high nibble first */
+  const uint8_t* quals;    /* qual_bits == 4: 4-bit codes into qual_dict, laid out like bases4;
+                              qual_bits == 8: Phred bytes at read_off[], as ma_batch_t::read_quals */
+  int32_t qual_bits;       /* 4 or 8 */
+  uint8_t qual_dict[16];   /* Phred value of each 4-bit code (qual_bits == 4) */
+} ma_packed_reads_t;
+
 typedef struct ma_ctx ma_ctx_t;
 
 int ma_create(const ma_params_t* prm, int device, int memspace, ma_ctx_t** out);
@@ -269,6 +291,20 @@ int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out
  * the struct's address, window and read counts) has returned; the arrays should be page-locked (hipHostMalloc /
  * hipHostRegister), a copy from pageable memory is slow.  At most two batches wait at a time; further calls do nothing. */
 int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next);
+
+/* ma_process_stats_batch / ma_prefetch_batch on packed reads.  b->read_bases and b->read_quals must be NULL (MA_ERR_ARG
+ * otherwise: a batch is either ASCII or packed); pk == NULL, a NULL member of it or a qual_bits other than 4 and 8 are
+ * MA_ERR_ARG too.  Everything else is ma_process_stats_batch's: fmt is optional, the same lanes, caps and status flags.  Both
+ * memory spaces: with MA_MEM_DEVICE pk's two pointers are device pointers (the struct itself is always in host memory) and
+ * the expansion goes into workspace of the context.  A prefetched batch is recognised by the batch struct's address, its
+ * counts AND pk's address: a batch queued as ASCII and brought packed, or the other way round, is dropped and computed in
+ * the call, like one queued for other optional outputs.  pk and its arrays stay unchanged as long as `next` must.
+ * The single-stage calls (ma_repeat_gate_batch, ma_assemble_batch, ma_msa_batch, ma_genotype_batch, ma_genotype_stats_batch,
+ * ma_annotate_batch) do not take the packed form. */
+int ma_process_packed_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* gate,
+                            const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno,
+                            const ma_fmt_out_t* fmt);
+int ma_prefetch_packed_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* next_pk);
 
 /* Kernel timing mode: 0 = off, 1 = reset at every API call (default), 2 = accumulate across calls
  * until ma_timing_control is called again (used by bench.py to time kernels over the timed region), 3 = as 2 and

@@ -69,6 +69,14 @@ class FmtOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ev_sums", "fmt_npbq", "fmt_cmlod", "fmt_stat")]
 
 
+class PackedReads(C.Structure):
+    """ma_packed_reads_t"""
+    _fields_ = [("bases4", C.c_void_p), ("quals", C.c_void_p), ("qual_bits", C.c_int32), ("qual_dict", C.c_uint8 * 16)]
+
+
+BASE_CODES = "=ACMGRSVTWYHKDBN"  # BAM's 4-bit base codes
+
+
 def load_cdll(path=None):
     """dlopen the product library.  PyTorch's ROCm wheels bundle their own HIP runtime (torch/lib/libamdhip64.so, no
     SONAME), libmicroasm.so is linked against the system one: whichever of the two initialises second in a process
@@ -166,3 +174,91 @@ def make_batch_struct(arrs, n_windows, n_reads):
     b.n_windows = n_windows
     b.n_reads = n_reads
     return b
+
+
+def _pack_nibbles(codes, read_off):
+    """4-bit codes (one per element, absolute positions of read_off) -> the nibble array of include/microasm.h: read r
+    starts at byte (read_off[r] + r) >> 1, high nibble first."""
+    off = np.asarray(read_off, dtype=np.int64)
+    nr = len(off) - 1
+    total = int(off[-1]) if nr > 0 else 0
+    out = np.zeros((total + nr + 1) // 2, dtype=np.uint8)
+    if total == 0:
+        return out
+    lens = off[1:] - off[:-1]
+    read_of = np.repeat(np.arange(nr, dtype=np.int64), lens)
+    within = np.arange(total, dtype=np.int64) - off[read_of]
+    start = (off[:-1] + np.arange(nr, dtype=np.int64)) >> 1
+    byte = start[read_of] + (within >> 1)
+    shift = np.where(within & 1, 0, 4).astype(np.uint8)
+    np.bitwise_or.at(out, byte, (codes.astype(np.uint8) & 15) << shift)
+    return out
+
+
+def unpack_nibbles(packed, read_off):
+    """the inverse of _pack_nibbles: one 4-bit code per element"""
+    off = np.asarray(read_off, dtype=np.int64)
+    nr = len(off) - 1
+    total = int(off[-1]) if nr > 0 else 0
+    if total == 0:
+        return np.zeros(0, dtype=np.uint8)
+    lens = off[1:] - off[:-1]
+    read_of = np.repeat(np.arange(nr, dtype=np.int64), lens)
+    within = np.arange(total, dtype=np.int64) - off[read_of]
+    start = (off[:-1] + np.arange(nr, dtype=np.int64)) >> 1
+    b = packed[start[read_of] + (within >> 1)]
+    return np.where(within & 1, b & 15, b >> 4).astype(np.uint8)
+
+
+def pack_reads(arrs, qual_bits=None):
+    """The read bases and qualities of a batch (dict of BATCH_DTYPES arrays) as ma_packed_reads_t wants them.  Bases that are
+    none of BAM's sixteen letters (lower case included) become N, as in a BAM file.  qual_bits=None: 4 when the batch holds
+    at most 16 distinct Phred values, else 8; asking for 4 with more than 16 raises.  Returns (packed, twin): packed =
+    dict(bases4, quals, qual_bits, qual_dict), twin = a copy of `arrs` whose read_bases / read_quals are what the device
+    decodes -- the input of the equivalent plain call."""
+    read_off = np.asarray(arrs["read_off"], dtype=np.uint64)
+    total = int(read_off[-1]) if len(read_off) > 1 else 0
+    bases = np.asarray(arrs["read_bases"], dtype=np.uint8)[:total]
+    quals = np.asarray(arrs["read_quals"], dtype=np.uint8)[:total]
+    code_of = np.full(256, 15, dtype=np.uint8)
+    for i, ch in enumerate(BASE_CODES):
+        code_of[ord(ch)] = i
+    codes = code_of[bases]
+    letters = np.frombuffer(BASE_CODES.encode(), dtype=np.uint8)
+    distinct = np.unique(quals)
+    if qual_bits is None:
+        qual_bits = 4 if len(distinct) <= 16 else 8
+    if qual_bits not in (4, 8):
+        raise ValueError("qual_bits must be 4 or 8")
+    qual_dict = np.zeros(16, dtype=np.uint8)
+    if qual_bits == 4:
+        if len(distinct) > 16:
+            raise ValueError(f"{len(distinct)} distinct qualities do not fit 4 bits")
+        qual_dict[:len(distinct)] = distinct
+        packed_quals = _pack_nibbles(np.searchsorted(distinct, quals).astype(np.uint8), read_off)
+    else:
+        packed_quals = np.ascontiguousarray(arrs["read_quals"], dtype=np.uint8).copy()
+    packed = dict(bases4=_pack_nibbles(codes, read_off), quals=packed_quals, qual_bits=qual_bits, qual_dict=qual_dict)
+    twin = dict(arrs)
+    twin["read_bases"] = np.ascontiguousarray(arrs["read_bases"], dtype=np.uint8).copy()
+    twin["read_bases"][:total] = letters[codes]
+    twin["read_quals"] = np.ascontiguousarray(arrs["read_quals"], dtype=np.uint8).copy()
+    return packed, twin
+
+
+def make_packed_struct(packed):
+    """ma_packed_reads_t over pack_reads()'s dict (numpy arrays, torch tensors or raw device pointers; kept alive by the caller)"""
+    def ptr(a):
+        return a.ctypes.data if isinstance(a, np.ndarray) else (a if isinstance(a, int) else a.data_ptr())
+    s = PackedReads()
+    s.bases4 = ptr(packed["bases4"])
+    s.quals = ptr(packed["quals"])
+    s.qual_bits = int(packed["qual_bits"])
+    for i, v in enumerate(np.asarray(packed["qual_dict"], dtype=np.uint8)[:16]):
+        s.qual_dict[i] = int(v)
+    return s
+
+
+def packed_batch_arrays(arrs):
+    """the batch arrays of a packed call: everything but the read bases and qualities (those must be NULL)"""
+    return {k: v for k, v in arrs.items() if k not in ("read_bases", "read_quals")}

@@ -171,7 +171,7 @@ int stage_batch(ma_ctx* ctx, const ma_batch_t* b, DBatch* d) {
   for (int i = 0; i < 10; ++i) {
     if (i == 9 && !b->read_hint) break;
     MA_HIP(ctx, ctx->in_stage[i].reserve(items[i].bytes + items[i].pad + 16));
-    if (items[i].bytes)
+    if (items[i].bytes && items[i].src)  // (no source: a packed call, k_unpack_reads fills the array)
       MA_HIP(ctx, hipMemcpyAsync(ctx->in_stage[i].p, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
     if (items[i].pad)
       MA_HIP(ctx, hipMemsetAsync(static_cast<char*>(ctx->in_stage[i].p) + items[i].bytes, 0, items[i].pad, ctx->stream));
@@ -214,7 +214,7 @@ void advance_fields(S* s, const std::vector<OutField>& per_unit, size_t first, s
 }
 
 // One contiguous window range [w0, w1) of the batch on a child context.  All pointers are device pointers.
-int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, int w0, int w1, u32 r0, u32 r1, ma_gate_out_t g,
+int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, const DPacked* pk, int w0, int w1, u32 r0, u32 r1, ma_gate_out_t g,
              ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, ma_fmt_out_t f, int lane_index) {
   MA_HIP(ch, hipSetDevice(ch->device));
   MA_HIP(ch, hipStreamWaitEvent(ch->stream, start, 0));
@@ -243,6 +243,7 @@ int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, int w0, int w1, u
   advance_fields(&q, gf, 2, 6, r0);   // alignment / assignment taps: per read
   advance_fields(&q, gf, 6, 8, w0);   // PL, GQ: per window
   advance_fields(&f, fmt_fields(p, 1), 0, 99, w0);  // (all null without the statistics)
+  if (pk) MA_TRY_RC(launch_unpack(ch, *pk, d.read_off, r0, static_cast<u64>(r1) - r0));  // a packed call: the lane's reads first
   MA_TRY_RC(launch_gate(ch, d, g.max_approx, g.max_exact));
   MA_TRY_RC(launch_assemble(ch, d, a, g.max_approx));
   MA_TRY_RC(launch_msa(ch, d, a, v));
@@ -308,7 +309,7 @@ struct DevLanePool {
   }
 };
 
-int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const ma_gate_out_t& g, const ma_asm_out_t& a,
+int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk, const ma_gate_out_t& g, const ma_asm_out_t& a,
                      const ma_var_out_t& v, const ma_geno_out_t& q, const ma_fmt_out_t& f) {
   while (static_cast<int>(ctx->lanes.size()) < lanes) {
     ma_ctx* ch = new (std::nothrow) ma_ctx();
@@ -340,7 +341,7 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const ma_gate_out_
   }
   if (!ctx->dev_pool) ctx->dev_pool = new DevLanePool();
   static_cast<DevLanePool*>(ctx->dev_pool)->run(lanes, [&](int k) {
-    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, k);
+    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, pk, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, k);
   });
   for (int k = 0; k < lanes; ++k) {
     if (rc[k] != MA_OK) {
@@ -500,8 +501,10 @@ int run_copy_ops(ma_ctx* owner, hipStream_t stream, std::vector<CopyOp> const& o
 
 // Plan the upload of the slice [w0, w1) of a host batch into input set `set` of lane `ch`: buffers reserved, the copies
 // appended to `ops`; offsets stay absolute, the base pointers are moved back instead.  *d is the device view (valid once
-// the copies have run).
-int stage_lane_inputs(ma_ctx* ch, int set, const ma_batch_t* b, int w0, int w1, std::vector<CopyOp>* ops, DBatch* d) {
+// the copies have run).  A packed batch (pk): the nibble arrays of the slice go into bufs[10] / [11] in place of the read
+// bases and -- 4-bit -- qualities; bufs[4] / [5] get their zero pads only, *dpk says how k_unpack_reads fills the rest.
+int stage_lane_inputs(ma_ctx* ch, int set, const ma_batch_t* b, int w0, int w1, std::vector<CopyOp>* ops, DBatch* d,
+                      const ma_packed_reads_t* pk = nullptr, DPacked* dpk = nullptr) {
   int const n = w1 - w0;
   u32 const r0 = b->read_win_off[w0], r1 = b->read_win_off[w1];
   size_t const nr = static_cast<size_t>(r1) - r0;
@@ -516,8 +519,8 @@ int stage_lane_inputs(ma_ctx* ch, int set, const ma_batch_t* b, int w0, int w1, 
                           {b->ref_off + w0, 4ull * (n + 1), false},
                           {in.h_rwo.data(), 4ull * (n + 1), false},
                           {b->read_off + r0, 8ull * (nr + 1), false},
-                          {b->read_bases + b0, static_cast<size_t>(b1 - b0), true},
-                          {b->read_quals + b0, static_cast<size_t>(b1 - b0), true},
+                          {pk ? nullptr : b->read_bases + b0, static_cast<size_t>(b1 - b0), true},
+                          {pk ? (pk->qual_bits == 8 ? pk->quals + b0 : nullptr) : b->read_quals + b0, static_cast<size_t>(b1 - b0), true},
                           {b->read_qname_id + r0, 4 * nr, false},
                           {b->read_sample + r0, nr, false},
                           {b->read_flags + r0, nr, false},
@@ -529,9 +532,29 @@ int stage_lane_inputs(ma_ctx* ch, int set, const ma_batch_t* b, int w0, int w1, 
     MA_HIP(ch, in.bufs[i].reserve(front + items[i].bytes + kPad + 16));
     char* base = static_cast<char*>(in.bufs[i].p);
     if (front) ops->push_back(CopyOp{base, nullptr, front});
-    ops->push_back(CopyOp{base + front, items[i].src, items[i].bytes});
+    if (items[i].src || !pk || (i != 4 && i != 5)) ops->push_back(CopyOp{base + front, items[i].src, items[i].bytes});
     if (items[i].padded) ops->push_back(CopyOp{base + front + items[i].bytes, nullptr, kPad});
     dp[i] = base + front;
+  }
+  if (pk) {
+    // the slice's bytes of a nibble array: from the first byte of read r0 to the end of read r1 - 1; the kernel loads whole
+    // aligned dwords, so there is room (never looked at) on both sides
+    size_t const p0 = static_cast<size_t>((b0 + r0) >> 1), p1 = static_cast<size_t>((b1 + r1 + 1) >> 1);
+    const u8* srcs[2] = {pk->bases4, pk->qual_bits == 4 ? pk->quals : nullptr};
+    const u8* dev[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+      if (!srcs[i]) continue;
+      MA_HIP(ch, in.bufs[10 + i].reserve(kPad + (p1 - p0) + kPad));
+      char* base = static_cast<char*>(in.bufs[10 + i].p);
+      ops->push_back(CopyOp{base + kPad, srcs[i] + p0, nr ? p1 - p0 : 0});
+      dev[i] = reinterpret_cast<const u8*>(base + kPad) - p0;
+    }
+    *dpk = DPacked{};
+    dpk->bases4 = dev[0];
+    dpk->quals4 = dev[1];
+    dpk->out_bases = reinterpret_cast<u8*>(dp[4]) - b0;
+    dpk->out_quals = reinterpret_cast<u8*>(dp[5]) - b0;
+    set_unpack_luts(dpk, pk);
   }
   *d = DBatch{};
   d->n_windows = n;
@@ -591,6 +614,9 @@ struct HostJob {
   u32 mask = 0;                       // seg_table entries to compute and pack
   std::shared_ptr<UploadTask> upload; // the upload ma_prefetch_batch started (null: every lane uploads its slice)
   std::vector<DBatch> staged;         // the lanes' device views of that upload
+  bool packed = false;                // a packed batch: `pk` is a copy of the caller's struct, staged_pk the lanes' views
+  ma_packed_reads_t pk{};
+  std::vector<DPacked> staged_pk;
   const ma_geno_out_t* taps = nullptr;  // the caller's struct when it asked for the per-read taps (never on a job queued ahead)
   std::vector<LaneResult> res;
   std::mutex mu;
@@ -651,6 +677,7 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   u64 const b0 = b->read_off[r0], b1 = b->read_off[r1];
   R.w0 = w0; R.w1 = w1; R.r0 = r0; R.nr = nr;
   DBatch d{};
+  DPacked dpk{};
   if (job.upload) {
     job.upload->wait_lane(static_cast<size_t>(k));
     if (job.upload->rc != MA_OK) {
@@ -658,9 +685,10 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
       return job.upload->rc;
     }
     d = job.staged[k];
+    if (job.packed) dpk = job.staged_pk[k];
   } else {
     std::vector<CopyOp> ops;
-    MA_TRY_RC(stage_lane_inputs(ch, set, b, w0, w1, &ops, &d));
+    MA_TRY_RC(stage_lane_inputs(ch, set, b, w0, w1, &ops, &d, job.packed ? &job.pk : nullptr, &dpk));
     MA_TRY_RC(run_copy_ops(ch, ch->stream, ops, std::vector<size_t>(), [](size_t) {}));
   }
   // ---- device-side outputs of the lane (fixed strides, as the kernels write them) ----
@@ -686,6 +714,7 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     for (size_t i = 0; i < ff.size(); ++i) need_f[i] = (job.mask >> (kSegFmt0 + i)) & 1u;
     MA_TRY_RC(alloc_fields(ch, &o.f, ff, 44, need_f));
   }
+  if (job.packed) MA_TRY_RC(launch_unpack(ch, dpk, d.read_off, r0, nr));  // after the slice's copies, before the gate
   t_up = since();
   MA_TRY_RC(launch_gate(ch, d, o.g.max_approx, o.g.max_exact));
   t_gate = since();
@@ -775,7 +804,8 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     fprintf(stderr, "[microasm] t=%.1f host lane [%d, %d): enqueue-upload %.2f gate %.2f assemble %.2f msa %.2f genotype %.2f pack %.2f "
             "download %.2f ms; %.1f MB in, %.2f MB packed out\n", wall_ms(), w0, w1, t_up, t_gate - t_up, t_asm - t_gate,
             t_msa - t_asm, t_geno - t_msa, t_pack - t_geno, since() - t_pack,
-            (static_cast<double>(f1 - f0) + 2.0 * static_cast<double>(b1 - b0) + 21.0 * nr) / 1e6, packed_bytes / 1e6);
+            (static_cast<double>(f1 - f0) + (!job.packed ? 2.0 : (job.pk.qual_bits == 4 ? 1.0 : 1.5)) * static_cast<double>(b1 - b0) +
+             21.0 * nr) / 1e6, packed_bytes / 1e6);
   return MA_OK;
 }
 
@@ -959,6 +989,7 @@ std::vector<int> lane_bounds(int n_windows, int lanes) {
 // staged device views of a prefetched batch, per set and lane (parent context; kept beside pf_batch)
 struct PrefetchViews {
   std::vector<DBatch> d[2];
+  std::vector<DPacked> pk[2];  // (packed batches)
 };
 std::mutex g_views_mu;
 std::unordered_map<ma_ctx*, PrefetchViews> g_views;
@@ -972,8 +1003,8 @@ void forget_views(ma_ctx* ctx) {
 }
 
 // queue the lanes' jobs of batch `b`, whose inputs are (being) staged in `set` when `ready`
-std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, int set, std::shared_ptr<UploadTask> upload,
-                                     u32 mask, const ma_geno_out_t* taps) {
+std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, int set,
+                                     std::shared_ptr<UploadTask> upload, u32 mask, const ma_geno_out_t* taps) {
   HostAsync* ha = async_of(ctx);
   auto job = std::make_shared<HostJob>();
   job->batch = *b;
@@ -989,6 +1020,11 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
   job->mask = mask;
   job->upload = upload;
   if (upload) job->staged = views_of(ctx).d[set];
+  if (pk) {
+    job->packed = true;
+    job->pk = *pk;
+    if (upload) job->staged_pk = views_of(ctx).pk[set];
+  }
   job->taps = taps;
   job->res.resize(lanes);
   for (int k = 0; k < lanes; ++k) {
@@ -1002,8 +1038,8 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
   return job;
 }
 
-int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_gate_out_t* g, const ma_asm_out_t* a,
-                 const ma_var_out_t* v, const ma_geno_out_t* q, const ma_fmt_out_t* f) {
+int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* g,
+                 const ma_asm_out_t* a, const ma_var_out_t* v, const ma_geno_out_t* q, const ma_fmt_out_t* f) {
   MA_TRY_RC(ensure_workers(ctx, lanes));
   HostAsync* ha = async_of(ctx);
   OutPtrs const user{{g, a, v, q, f}};
@@ -1012,12 +1048,23 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_gate_out_
   // did ma_prefetch_batch upload this batch?  (the oldest set that holds it); otherwise any set that holds nothing
   int set = -1;
   bool prefetched = false;
-  for (int s = 0; s < 2; ++s)
-    if (ctx->pf_batch[s] == b && ctx->pf_sig[s][0] == b->n_windows && ctx->pf_sig[s][1] == b->n_reads && ctx->pf_sig[s][2] == lanes &&
-        (set < 0 || ctx->pf_seq[s] < ctx->pf_seq[set])) {
+  for (int s = 0; s < 2; ++s) {
+    if (ctx->pf_batch[s] != b || ctx->pf_sig[s][0] != b->n_windows || ctx->pf_sig[s][1] != b->n_reads || ctx->pf_sig[s][2] != lanes)
+      continue;
+    if (ctx->pf_pk[s] != pk) {  // queued as ASCII and brought packed, or the other way round: dropped, computed below
+      if (ha->jobs[s]) ha->jobs[s]->wait_all();
+      ha->jobs[s].reset();
+      if (ha->uploads[s]) ha->uploads[s]->wait();
+      ha->uploads[s].reset();
+      ctx->pf_batch[s] = nullptr;
+      ctx->pf_pk[s] = nullptr;
+      continue;
+    }
+    if (set < 0 || ctx->pf_seq[s] < ctx->pf_seq[set]) {
       set = s;
       prefetched = true;
     }
+  }
   if (set < 0) {
     set = !ctx->pf_batch[0] ? 0 : (!ctx->pf_batch[1] ? 1 : (ctx->pf_seq[0] < ctx->pf_seq[1] ? 0 : 1));
     if (ctx->pf_batch[set]) {  // both sets hold batches that were never processed: give the older one up
@@ -1026,6 +1073,7 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_gate_out_
       if (ha->uploads[set]) ha->uploads[set]->wait();
       ha->uploads[set].reset();
       ctx->pf_batch[set] = nullptr;
+      ctx->pf_pk[set] = nullptr;
     }
   }
   std::shared_ptr<HostJob> job = ha->jobs[set];
@@ -1035,7 +1083,7 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_gate_out_
     job.reset();
   }
   if (!prefetched) ha->uploads[set].reset();
-  if (!job) job = submit_host(ctx, lanes, b, set, prefetched ? ha->uploads[set] : nullptr, mask, taps ? q : nullptr);
+  if (!job) job = submit_host(ctx, lanes, b, pk, set, prefetched ? ha->uploads[set] : nullptr, mask, taps ? q : nullptr);
   ha->jobs[set] = job;
   ha->last_mask = mask;
   ha->have_mask = true;
@@ -1068,6 +1116,7 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_gate_out_
   ha->jobs[set].reset();
   ha->uploads[set].reset();
   ctx->pf_batch[set] = nullptr;  // consumed (or used as plain staging): free for the next prefetch
+  ctx->pf_pk[set] = nullptr;
   return rc;
 }
 
@@ -1129,6 +1178,7 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->spec_data.release(); ctx->spec_out.release(); ctx->spec_nodes.release();
   ctx->ws_aln.release(); ctx->ws_misc.release(); ctx->ws_cx.release(); ctx->ws_gen.release(); ctx->ws_mm.release(); ctx->dev_stats.release();
   ctx->pack_aux.release();
+  ctx->ws_unpack.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
     pp = nullptr;
@@ -1376,7 +1426,14 @@ int ma_annotate_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* as
   return MA_OK;
 }
 
-int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
+// a packed call's arguments: the batch is either ASCII or packed
+static int check_packed(const ma_batch_t* b, const ma_packed_reads_t* pk) {
+  if (!b || !pk || b->read_bases || b->read_quals) return MA_ERR_ARG;
+  if ((pk->qual_bits != 4 && pk->qual_bits != 8) || !pk->bases4 || !pk->quals) return MA_ERR_ARG;
+  return MA_OK;
+}
+
+static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* pk) {
   if (!ctx || !next) return MA_ERR_ARG;
   if (ctx->memspace != MA_MEM_HOST || next->n_windows <= 0 || getenv("MA_HOST_LEGACY")) return MA_OK;  // nothing to stage
   MA_HIP(ctx, hipSetDevice(ctx->device));
@@ -1389,13 +1446,14 @@ int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
   std::vector<int> const wb = lane_bounds(next->n_windows, lanes);
   PrefetchViews& pv = views_of(ctx);
   pv.d[set].assign(lanes, DBatch{});
+  pv.pk[set].assign(lanes, DPacked{});
   auto task = std::make_shared<UploadTask>();
   for (int k = 0; k < lanes; ++k) {
     if (wb[k + 1] <= wb[k]) {
       task->lane_end.push_back(task->ops.size());
       continue;
     }
-    int const rc = stage_lane_inputs(ctx->lanes[k], set, next, wb[k], wb[k + 1], &task->ops, &pv.d[set][k]);
+    int const rc = stage_lane_inputs(ctx->lanes[k], set, next, wb[k], wb[k + 1], &task->ops, &pv.d[set][k], pk, &pv.pk[set][k]);
     if (rc != MA_OK) {
       ma_set_err(ctx, "prefetch, lane " + std::to_string(k) + ": " + ma_get_err(ctx->lanes[k]));
       return rc;
@@ -1411,6 +1469,7 @@ int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
   ha->up_cv.notify_one();
   ha->uploads[set] = task;
   ctx->pf_batch[set] = next;
+  ctx->pf_pk[set] = pk;
   ctx->pf_sig[set][0] = next->n_windows;
   ctx->pf_sig[set][1] = next->n_reads;
   ctx->pf_sig[set][2] = lanes;
@@ -1419,8 +1478,16 @@ int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) {
   // waiting (or on their way).  Not in the statistics-gathering mode of the bench (its device counters are per call).
   ha->jobs[set].reset();
   if (ha->have_mask && !ctx->collect)
-    ha->jobs[set] = submit_host(ctx, lanes, next, set, task, ha->last_mask, nullptr);
+    ha->jobs[set] = submit_host(ctx, lanes, next, pk, set, task, ha->last_mask, nullptr);
   return MA_OK;
+}
+
+int ma_prefetch_batch(ma_ctx_t* ctx, const ma_batch_t* next) { return prefetch_any(ctx, next, nullptr); }
+
+int ma_prefetch_packed_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* next_pk) {
+  if (!ctx) return MA_ERR_ARG;
+  MA_TRY(check_packed(next, next_pk));
+  return prefetch_any(ctx, next, next_pk);
 }
 
 int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
@@ -1428,8 +1495,54 @@ int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* ga
   return ma_process_stats_batch(ctx, b, gate, asmb, vars, geno, nullptr);
 }
 
-int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
-                           const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt) {
+// MA_MEM_DEVICE (and the legacy host staging) of a packed call: where k_unpack_reads finds the nibble arrays of the whole
+// batch and where it writes -- offsets are the batch's own, pads as the stages expect them.  *d comes from stage_batch.
+static int stage_packed(ma_ctx* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, DBatch* d, DPacked* dp) {
+  size_t const nr = static_cast<size_t>(b->n_reads);
+  constexpr size_t kPad = 64;
+  *dp = DPacked{};
+  set_unpack_luts(dp, pk);
+  if (ctx->memspace == MA_MEM_DEVICE) {
+    u64 total = 0;
+    if (nr) {
+      MA_HIP(ctx, hipMemcpyAsync(&total, b->read_off + nr, 8, hipMemcpyDeviceToHost, ctx->stream));
+      MA_HIP(ctx, ma_stream_sync(ctx));
+    }
+    size_t const arr = kPad + static_cast<size_t>(total) + kPad, slot = (arr + 255) & ~size_t(255);
+    int const narr = pk->qual_bits == 4 ? 2 : 1;
+    MA_HIP(ctx, ctx->ws_unpack.reserve(slot * narr));
+    u8* base = ctx->ws_unpack.as<u8>();
+    for (int i = 0; i < narr; ++i) {
+      MA_HIP(ctx, hipMemsetAsync(base + slot * i, 0, kPad, ctx->stream));
+      MA_HIP(ctx, hipMemsetAsync(base + slot * i + kPad + total, 0, kPad, ctx->stream));
+    }
+    dp->bases4 = pk->bases4;
+    dp->quals4 = pk->qual_bits == 4 ? pk->quals : nullptr;
+    dp->out_bases = base + kPad;
+    dp->out_quals = narr == 2 ? base + slot + kPad : nullptr;
+    d->read_bases = dp->out_bases;
+    d->read_quals = narr == 2 ? dp->out_quals : pk->quals;
+    return MA_OK;
+  }
+  // host arrays, legacy staging: stage_batch reserved in_stage[4] / [5] (and copied 8-bit qualities); the nibble arrays follow
+  size_t const total = nr ? b->read_off[nr] : 0, bytes = (total + nr + 1) / 2;
+  const u8* srcs[2] = {pk->bases4, pk->qual_bits == 4 ? pk->quals : nullptr};
+  const u8* dev[2] = {nullptr, nullptr};
+  for (int i = 0; i < 2; ++i) {
+    if (!srcs[i]) continue;
+    MA_HIP(ctx, ctx->in_stage[10 + i].reserve(bytes + 16));
+    if (bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->in_stage[10 + i].p, srcs[i], bytes, hipMemcpyHostToDevice, ctx->stream));
+    dev[i] = ctx->in_stage[10 + i].as<u8>();
+  }
+  dp->bases4 = dev[0];
+  dp->quals4 = dev[1];
+  dp->out_bases = ctx->in_stage[4].as<u8>();
+  dp->out_quals = ctx->in_stage[5].as<u8>();
+  return MA_OK;
+}
+
+static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* gate,
+                       const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt) {
   MA_BEGIN(ctx);
   if (!gate || !asmb || !vars || !geno) return MA_ERR_ARG;
   if (!gate->max_approx || !gate->max_exact || !geno->allele_counts || !geno->var_qual) return MA_ERR_ARG;
@@ -1441,10 +1554,19 @@ int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out
     if (!asmb->win_status || !asmb->win_ncomp || !asmb->comp_hap0 || !asmb->comp_nhaps || !asmb->hap_len ||
         !asmb->hap_nruns || !vars->win_nvars)
       return MA_ERR_ARG;
-    return process_host(ctx, host_lanes(ctx, b->n_windows), b, gate, asmb, vars, geno, fmt);
+    return process_host(ctx, host_lanes(ctx, b->n_windows), b, pk, gate, asmb, vars, geno, fmt);
   }
   DBatch d;
-  MA_TRY(stage_batch(ctx, b, &d));
+  DPacked dp{};
+  if (pk) {
+    if (b->n_windows <= 0) return b->n_windows == 0 ? MA_OK : MA_ERR_ARG;
+    ma_batch_t bb = *b;
+    if (pk->qual_bits == 8) bb.read_quals = pk->quals;
+    MA_TRY(stage_batch(ctx, &bb, &d));
+    MA_TRY(stage_packed(ctx, b, pk, &d, &dp));
+  } else {
+    MA_TRY(stage_batch(ctx, b, &d));
+  }
   OutMirror<ma_gate_out_t> g;
   MA_TRY(g.prepare(ctx, gate, gate_fields(ctx->prm, d.n_windows), 0, false));
   OutMirror<ma_asm_out_t> a;
@@ -1467,12 +1589,13 @@ int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out
     return d.n_windows >= 8192 && hwq >= 6 ? (single_k ? 2 : 4) : (d.n_windows >= 6144 ? 3 : (d.n_windows >= 2048 ? 2 : 1));
   });
   if (lanes <= 1) {
+    if (pk) MA_TRY(launch_unpack(ctx, dp, d.read_off, 0, static_cast<u64>(d.n_reads)));
     MA_TRY(launch_gate(ctx, d, g.dev.max_approx, g.dev.max_exact));
     MA_TRY(launch_assemble(ctx, d, a.dev, g.dev.max_approx));
     MA_TRY(launch_msa(ctx, d, a.dev, v.dev));
     MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, q.dev, &f.dev));
   } else {
-    MA_TRY(process_in_lanes(ctx, lanes, d, g.dev, a.dev, v.dev, q.dev, f.dev));
+    MA_TRY(process_in_lanes(ctx, lanes, d, pk ? &dp : nullptr, g.dev, a.dev, v.dev, q.dev, f.dev));
   }
   MA_TRY(g.download(ctx));
   MA_TRY(a.download(ctx));
@@ -1481,6 +1604,19 @@ int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out
   MA_TRY(f.download(ctx));
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
   return MA_OK;
+}
+
+int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
+                           const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt) {
+  return process_any(ctx, b, nullptr, gate, asmb, vars, geno, fmt);
+}
+
+int ma_process_packed_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* gate,
+                            const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno,
+                            const ma_fmt_out_t* fmt) {
+  if (!ctx) return MA_ERR_ARG;
+  MA_TRY(check_packed(b, pk));
+  return process_any(ctx, b, pk, gate, asmb, vars, geno, fmt);
 }
 
 }  // extern "C"

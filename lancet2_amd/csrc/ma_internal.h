@@ -52,7 +52,7 @@ struct DevBuf {
 // One staged copy of a lane's slice of a host batch (MA_MEM_HOST route of ma_process_batch): two per lane, so that
 // ma_prefetch_batch can upload the next batch while this one computes.
 struct InputSet {
-  DevBuf bufs[10];
+  DevBuf bufs[12];  // [0..9] the batch arrays as the stages read them; [10], [11] the nibble arrays of a packed call
   std::vector<uint32_t> h_rwo;  // the lane's rebased read_win_off while its upload is in flight
 };
 
@@ -72,7 +72,8 @@ struct ma_ctx {
   std::string err;     // last error: written through ma_set_err (worker threads of the host route write it too)
   std::mutex err_mu;
   // staging for MA_MEM_HOST
-  ma::DevBuf in_stage[10];
+  ma::DevBuf in_stage[12];  // ([10], [11]: the nibble arrays of a packed call)
+  ma::DevBuf ws_unpack;     // MA_MEM_DEVICE packed call: the expanded read bases (and 4-bit qualities)
   std::vector<ma::DevBuf> out_stage;
   // per-stage workspaces (grow-only, reused across calls)
   ma::DevBuf ws_build, ws_nodes, ws_clean, ws_aln, ws_misc, ws_gen, ws_mm;  // (ws_build: the assembly stage's arena, then the POA stage's)
@@ -119,6 +120,7 @@ struct ma_ctx {
   // and the stream the uploads of a prefetch run on (api.hip: uploader thread)
   const ma_batch_t* pf_batch[2] = {nullptr, nullptr};
   int64_t pf_sig[2][3] = {{0, 0, 0}, {0, 0, 0}};  // n_windows, n_reads, lanes of the prefetched batch
+  const ma_packed_reads_t* pf_pk[2] = {nullptr, nullptr};  // ... and the packed-reads struct it came with (null: ASCII)
   unsigned long long pf_seq[2] = {0, 0}, pf_counter = 0;
   hipStream_t copy_stream = nullptr;
 
@@ -194,6 +196,21 @@ struct DBatch {
   const u8* read_flags;
   const i32* read_hint;  // may be null
 };
+
+// A packed call's reads (ma_packed_reads_t) on the device, for k_unpack_reads (unpack.hip).  bases4 / quals4 are addressed
+// with the batch's absolute nibble-array byte offsets, out_bases / out_quals with its absolute read_off values: a lane's
+// slice keeps the offsets and moves the base pointers back, as DBatch does.
+struct DPacked {
+  const u8* bases4;
+  const u8* quals4;   // null with qual_bits == 8: the Phred bytes are copied, not expanded
+  u8* out_bases;
+  u8* out_quals;
+  u32 base_lut[4];    // "=ACMGRSVTWYHKDBN", entry i in byte i & 3 of dword i >> 2
+  u32 qual_lut[4];    // qual_dict, likewise
+};
+void set_unpack_luts(DPacked* d, const ma_packed_reads_t* pk);
+// expand the reads [first, first + n) of the batch; read_off points at the entry of read `first`
+int launch_unpack(ma_ctx* ctx, const DPacked& d, const u64* read_off, u64 first, u64 n);
 
 int launch_gate(ma_ctx* ctx, const DBatch& b, u32* max_approx, u32* max_exact);
 int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& o, const u32* gate_approx);

@@ -36,6 +36,9 @@ def load_library(path=None):
     lib.ma_genotype_stats_batch.argtypes = [C.c_void_p] * 6
     lib.ma_process_stats_batch.argtypes = [C.c_void_p] * 7
     lib.ma_prefetch_batch.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ma_process_packed_batch"):  # (absent from a build of before the packed calls given as `path` for an A/B)
+        lib.ma_process_packed_batch.argtypes = [C.c_void_p] * 8
+        lib.ma_prefetch_packed_batch.argtypes = [C.c_void_p] * 3
     lib.ma_annotate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.ma_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     lib.ma_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
@@ -190,6 +193,23 @@ class Engine:
                                                     C.byref(capi.fill_struct(capi.FmtOut, f))), "ma_process_stats_batch")
         return g, a, v, q, f
 
+    def process_packed(self, arrs, n, nr, packed, debug=False, fields=None):
+        """ma_process_packed_batch: process_stats() on packed reads (capi.pack_reads; the read_bases / read_quals of `arrs`,
+        if any, are not passed).  Returns (gate, asm, var, geno, fmt)."""
+        g = self._alloc(capi.gate_out_spec(n))
+        a = self._alloc(capi.asm_out_spec(self.p, n))
+        v = self._alloc(capi.var_out_spec(self.p, n))
+        q = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))
+        f = self._alloc({k: s for k, s in capi.fmt_out_spec(self.p, n).items() if fields is None or k in fields})
+        b = capi.make_batch_struct(capi.packed_batch_arrays(arrs), n, nr)
+        pk = capi.make_packed_struct(packed)
+        self._check(self.lib.ma_process_packed_batch(self.h, C.byref(b), C.byref(pk), C.byref(capi.fill_struct(capi.GateOut, g)),
+                                                     C.byref(capi.fill_struct(capi.AsmOut, a)),
+                                                     C.byref(capi.fill_struct(capi.VarOut, v)),
+                                                     C.byref(capi.fill_struct(capi.GenoOut, q)),
+                                                     C.byref(capi.fill_struct(capi.FmtOut, f))), "ma_process_packed_batch")
+        return g, a, v, q, f
+
     # ---- device-resident path (MA_MEM_DEVICE): dicts of torch tensors (or raw int pointers) ----
     def process_device(self, batch_struct, gate, asm, var, geno):
         self._check(self.lib.ma_process_batch(self.h, C.byref(batch_struct), C.byref(gate), C.byref(asm),
@@ -202,6 +222,17 @@ class Engine:
     def prefetch(self, batch_struct):
         """MA_MEM_HOST: start uploading the batch that the next process_device() call will be given (ma_prefetch_batch)."""
         self._check(self.lib.ma_prefetch_batch(self.h, C.byref(batch_struct)), "ma_prefetch_batch")
+
+    def process_packed_device(self, batch_struct, packed_struct, gate, asm, var, geno, fmt=None):
+        """ma_process_packed_batch on caller-made structs (either memory space); fmt=None: without the statistics"""
+        self._check(self.lib.ma_process_packed_batch(self.h, C.byref(batch_struct), C.byref(packed_struct), C.byref(gate),
+                                                     C.byref(asm), C.byref(var), C.byref(geno),
+                                                     C.byref(fmt) if fmt is not None else None), "ma_process_packed_batch")
+
+    def prefetch_packed(self, batch_struct, packed_struct):
+        """MA_MEM_HOST: ma_prefetch_packed_batch -- prefetch() for the batch the next process_packed_device() call brings"""
+        self._check(self.lib.ma_prefetch_packed_batch(self.h, C.byref(batch_struct), C.byref(packed_struct)),
+                    "ma_prefetch_packed_batch")
 
     def annotate_device(self, batch_struct, asm, var, cx, gc_frac=0.41):
         self._check(self.lib.ma_annotate_batch(self.h, C.byref(batch_struct), C.byref(asm), C.byref(var),

@@ -93,6 +93,10 @@ struct SamRecord {
   int64_t mate_pos0 = -1;
   int64_t tlen = 0;
   std::string seq;
+  std::vector<uint8_t> seq4;  // a BAM source opened with keep_packed (--packed-reads): the record's (l_seq + 1) / 2 sequence bytes, `seq` stays empty
+  uint32_t l_seq4 = 0;
+  bool packed = false;
+  size_t SeqLen() const { return packed ? l_seq4 : seq.size(); }
   std::vector<uint8_t> qual;
   std::string md;
   bool has_md = false, has_sa = false;
@@ -342,7 +346,7 @@ class AlignmentSource {
             done = true;  // coordinate-sorted: nothing further in this chunk (or any later one) overlaps
             continue;
           }
-          SamRecord rec = DecodeBamRecord(buf.data(), buf.size(), ref_map_);
+          SamRecord rec = DecodeBamRecord(buf.data(), buf.size(), ref_map_, keep_packed_);
           if (rec.pos0 + rec.RefSpan() > s0) fn(rec);
         }
         if (done) break;
@@ -408,7 +412,8 @@ class AlignmentSource {
   }
 
   // one BAM alignment record (SAM specification 4.2; `b` points behind its block_size field)
-  static SamRecord DecodeBamRecord(const unsigned char* b, size_t block, std::vector<int> const& ref_map) {
+  // keep_packed: the sequence stays as the file has it (SamRecord::seq4: 4-bit codes, high nibble first), `seq` stays empty
+  static SamRecord DecodeBamRecord(const unsigned char* b, size_t block, std::vector<int> const& ref_map, bool keep_packed = false) {
     static const char* kSeq = "=ACMGRSVTWYHKDBN";
     static const char* kOps = "MIDNSHP=X";
     auto rd32 = [&](size_t at) { int32_t v; std::memcpy(&v, b + at, 4); return v; };
@@ -440,8 +445,14 @@ class AlignmentSource {
       r.cigar.push_back({(v & 15u) < 9 ? kOps[v & 15u] : '?', v >> 4});
     }
     p += 4u * n_cigar;
-    r.seq.resize(static_cast<size_t>(l_seq));
-    for (int32_t i = 0; i < l_seq; ++i) r.seq[static_cast<size_t>(i)] = kSeq[(b[p + static_cast<size_t>(i) / 2] >> (i % 2 ? 0 : 4)) & 15];
+    if (keep_packed) {  // copied, not decoded: the engine takes BAM's codes (ma_packed_reads_t)
+      r.seq4.assign(b + p, b + p + (static_cast<size_t>(l_seq) + 1) / 2);
+      r.l_seq4 = static_cast<uint32_t>(l_seq);
+      r.packed = true;
+    } else {
+      r.seq.resize(static_cast<size_t>(l_seq));
+      for (int32_t i = 0; i < l_seq; ++i) r.seq[static_cast<size_t>(i)] = kSeq[(b[p + static_cast<size_t>(i) / 2] >> (i % 2 ? 0 : 4)) & 15];
+    }
     p += static_cast<size_t>(l_seq + 1) / 2;
     r.qual.assign(b + p, b + p + l_seq);
     p += static_cast<size_t>(l_seq);
@@ -477,7 +488,7 @@ class AlignmentSource {
 
 #ifdef LANCET2_AMD_WITH_ZLIB
   // BAM: BGZF blocks are gzip members; the payload is the BAM record stream of the SAM specification, section 4.2
-  static AlignmentSource LoadBam(const std::string& path, Reference const& ref) {
+  static AlignmentSource LoadBam(const std::string& path, Reference const& ref, bool keep_packed = false) {
     std::ifstream in(path, std::ios::binary);
     if (!in) throw std::runtime_error("cannot open alignments " + path);
     std::vector<unsigned char> comp((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
@@ -521,14 +532,15 @@ class AlignmentSource {
       size_t const b = at + 4;
       at = b + static_cast<size_t>(block);
       if (at > raw.size()) break;
-      src.recs.push_back(DecodeBamRecord(raw.data() + b, static_cast<size_t>(block), ref_map));
+      src.recs.push_back(DecodeBamRecord(raw.data() + b, static_cast<size_t>(block), ref_map, keep_packed));
     }
     src.Finish(ref.chroms.size());
     return src;
   }
   // BAM + .bai: header only; records are fetched per region (ForRegion)
-  static AlignmentSource OpenIndexedBam(const std::string& path, const std::string& bai_path, Reference const& ref) {
+  static AlignmentSource OpenIndexedBam(const std::string& path, const std::string& bai_path, Reference const& ref, bool keep_packed = false) {
     AlignmentSource src;
+    src.keep_packed_ = keep_packed;
     src.index_ = std::make_shared<BamIndex>(BamIndex::Load(bai_path));
     src.path_ = path;
     src.bgzf_ = std::make_shared<BgzfFile>(path);
@@ -561,6 +573,7 @@ class AlignmentSource {
     c.bgzf_ = std::make_shared<BgzfFile>(path_);
     c.ref_map_ = ref_map_;
     c.chrom_rid_ = chrom_rid_;
+    c.keep_packed_ = keep_packed_;
     return c;
   }
   bool indexed() const { return bgzf_ != nullptr; }
@@ -576,6 +589,7 @@ class AlignmentSource {
   std::string path_;
   std::vector<int> ref_map_;    // BAM reference id -> chromosome of the FASTA (-1: not in it)
   std::vector<int> chrom_rid_;  // and back
+  bool keep_packed_ = false;    // --packed-reads: records keep their sequence bytes undecoded (for ReadCollector::Params::packed_reads)
 #endif
 };
 
@@ -836,6 +850,7 @@ class ReadCollector {
   struct Params {
     double max_sample_cov = 1000.0;  // core/read_collector.h:27
     bool extract_pairs = false;
+    bool packed_reads = false;  // CollectFlat emits the read bases as 4-bit codes (FlatBatch::seq4) instead of letters
   };
   struct Result {
     std::vector<Read> reads;
@@ -962,8 +977,26 @@ using ByteVec = std::vector<uint8_t>;
 #else
 using ByteVec = std::vector<uint8_t, NoInitAlloc<uint8_t>>;
 #endif
+// BAM's 4-bit code of a base letter; a letter that is none of "=ACMGRSVTWYHKDBN" (lower case included) is N, as in a BAM file
+inline uint8_t BaseCode4(uint8_t letter) {
+  static const std::array<uint8_t, 256> code_of = [] {
+    std::array<uint8_t, 256> t{};
+    t.fill(15);
+    const char* letters = "=ACMGRSVTWYHKDBN";
+    for (int i = 0; i < 16; ++i) t[static_cast<uint8_t>(letters[i])] = static_cast<uint8_t>(i);
+    return t;
+  }();
+  return code_of[letter];
+}
 struct FlatBatch {
   ByteVec ref_bases, read_bases, read_quals;
+  // packed_mode (ReadCollector::Params::packed_reads): read_bases stays empty.  A one-window batch of CollectFlat holds its
+  // reads' 4-bit sequence bytes back to back in seq4 (read i: [seq4_off[i], seq4_off[i + 1]), (len + 1) / 2 bytes -- a BAM
+  // record's own bytes, SAM text packed); CopyPlaced() copies each to its place in the batch's nibble array, bases4: byte
+  // (read_off[r] + r) >> 1 (include/microasm.h: ma_packed_reads_t).  Add() and Append() work on letters and refuse such a batch.
+  bool packed_mode = false;
+  ByteVec seq4;
+  std::vector<uint64_t> seq4_off{0};
   std::vector<uint8_t> read_sample, read_flags;
   std::vector<uint32_t> ref_off{0}, read_win_off{0}, read_qname_id;
   std::vector<uint64_t> read_off{0};
@@ -972,6 +1005,7 @@ struct FlatBatch {
   std::vector<std::vector<double>> sample_cov;  // [window][sample] sampled bases / window length
   ma_batch_t view{};
   void Add(Window const& w, std::string_view ref_seq, std::vector<Read> const& reads, std::vector<SampleInfo> const* samples = nullptr) {
+    if (packed_mode) throw std::logic_error("FlatBatch::Add: a packed_mode batch is built by CollectFlat + PlaceHeader / CopyPlaced only");
     windows.push_back(w);
     sample_cov.emplace_back();
     if (samples)
@@ -1000,6 +1034,7 @@ struct FlatBatch {
   // Appends the windows of another (unsealed) batch -- what Add() on their reads would have appended: the extract stage's
   // workers flatten each window on their own thread, the ordered assembler only copies.
   void Append(FlatBatch const& o) {
+    if (packed_mode || o.packed_mode) throw std::logic_error("FlatBatch::Append: not for packed_mode batches (PlaceHeader / CopyPlaced)");
     uint32_t const rb = static_cast<uint32_t>(ref_bases.size()), nr = static_cast<uint32_t>(read_qname_id.size());
     uint64_t const qb = read_bases.size();
     windows.insert(windows.end(), o.windows.begin(), o.windows.end());
@@ -1030,14 +1065,15 @@ struct FlatBatch {
     sample_cov.insert(sample_cov.end(), o.sample_cov.begin(), o.sample_cov.end());
     placed_ref_ += o.ref_bases.size();
     placed_reads_ += o.read_qname_id.size();
-    placed_bases_ += o.read_bases.size();
+    placed_bases_ += o.read_off.back();
     ref_off.push_back(static_cast<uint32_t>(placed_ref_));
     read_win_off.push_back(static_cast<uint32_t>(placed_reads_));
     return pl;
   }
   void SizeForPlaced() {
     ref_bases.resize(placed_ref_);
-    read_bases.resize(placed_bases_);
+    if (packed_mode) bases4.assign(std::max<size_t>((placed_bases_ + placed_reads_ + 1) / 2, 1), 0);
+    else read_bases.resize(placed_bases_);
     read_quals.resize(placed_bases_);
     read_sample.resize(placed_reads_);
     read_flags.resize(placed_reads_);
@@ -1050,7 +1086,13 @@ struct FlatBatch {
     if (!o.ref_bases.empty()) std::memcpy(ref_bases.data() + pl.ref0, o.ref_bases.data(), o.ref_bases.size());
     size_t const nr = o.read_qname_id.size();
     if (nr == 0) return;
-    std::memcpy(read_bases.data() + pl.base0, o.read_bases.data(), o.read_bases.size());
+    if (packed_mode) {
+      for (size_t i = 0; i < nr; ++i)  // reads start on byte boundaries: whole bytes, wherever the window lands in the batch
+        std::memcpy(bases4.data() + ((pl.base0 + o.read_off[i] + pl.read0 + i) >> 1), o.seq4.data() + o.seq4_off[i],
+                    static_cast<size_t>(o.seq4_off[i + 1] - o.seq4_off[i]));
+    } else {
+      std::memcpy(read_bases.data() + pl.base0, o.read_bases.data(), o.read_bases.size());
+    }
     std::memcpy(read_quals.data() + pl.base0, o.read_quals.data(), o.read_quals.size());
     std::memcpy(read_sample.data() + pl.read0, o.read_sample.data(), nr);
     std::memcpy(read_flags.data() + pl.read0, o.read_flags.data(), nr);
@@ -1067,6 +1109,9 @@ struct FlatBatch {
     read_qname_id.clear(); read_hint.clear(); windows.clear(); sample_cov.clear();
     placed_ref_ = placed_reads_ = 0;
     placed_bases_ = 0;
+    seq4.clear(); seq4_off.assign(1, 0); bases4.clear(); quals_packed.clear();
+    packed = ma_packed_reads_t{};
+    packed_view = ma_batch_t{};
     view = ma_batch_t{};
   }
   void Reserve(size_t n_win, size_t n_ref, size_t n_reads, size_t n_bases) {  // (Append then never re-allocates and copies what it holds)
@@ -1075,9 +1120,9 @@ struct FlatBatch {
     read_sample.reserve(n_reads); read_flags.reserve(n_reads); read_qname_id.reserve(n_reads); read_hint.reserve(n_reads); read_off.reserve(n_reads + 1);
   }
   void Seal() {
-    size_t const rb = ref_bases.size(), qb = read_bases.size();
+    size_t const rb = ref_bases.size(), qb = read_quals.size();
     ref_bases.resize(rb + 64, 0);
-    read_bases.resize(qb + 64, 0);
+    read_bases.resize(read_bases.size() + 64, 0);
     read_quals.resize(qb + 64, 0);
     view.n_windows = static_cast<int32_t>(windows.size());
     view.n_reads = static_cast<int64_t>(read_qname_id.size());
@@ -1091,6 +1136,49 @@ struct FlatBatch {
     view.read_sample = read_sample.data();
     view.read_flags = read_flags.data();
     view.read_hint = read_hint.data();
+  }
+  // --packed-reads (include/microasm.h: ma_packed_reads_t), after Seal(): the batch's quality dictionary -- 4-bit codes into
+  // the distinct Phred values in ascending order when there are at most 16 of them, the Phred bytes as they are (qual_bits =
+  // 8) otherwise -- and, unless the batch was built in packed_mode (bases4 is in place then), the read bases packed from
+  // read_bases.  packed_view is `view` without the two ASCII arrays: what ma_process_packed_batch / ma_prefetch_packed_batch
+  // take beside `packed`.  The arrays hold at least one byte, so that a batch without read bases still has non-null members.
+  ByteVec bases4, quals_packed;
+  ma_packed_reads_t packed{};
+  ma_batch_t packed_view{};
+  void PackReads() {
+    size_t const nr = read_off.empty() ? 0 : read_off.size() - 1;
+    size_t const total = nr ? static_cast<size_t>(read_off[nr]) : 0, bytes = std::max<size_t>((total + nr + 1) / 2, 1);
+    packed = ma_packed_reads_t{};
+    std::array<uint8_t, 256> qcode{};
+    std::array<bool, 256> seen{};
+    for (size_t i = 0; i < total; ++i) seen[read_quals[i]] = true;
+    int distinct = 0;
+    for (int q = 0; q < 256; ++q) {
+      if (!seen[static_cast<size_t>(q)]) continue;
+      if (distinct < 16) {
+        packed.qual_dict[distinct] = static_cast<uint8_t>(q);
+        qcode[static_cast<size_t>(q)] = static_cast<uint8_t>(distinct);
+      }
+      ++distinct;
+    }
+    bool const q4 = distinct <= 16;
+    if (!q4) std::memset(packed.qual_dict, 0, sizeof(packed.qual_dict));
+    if (!packed_mode) bases4.assign(bytes, 0);
+    quals_packed.assign(q4 ? bytes : 1, 0);
+    for (size_t r = 0; r < nr; ++r) {
+      size_t const o0 = static_cast<size_t>(read_off[r]), len = static_cast<size_t>(read_off[r + 1]) - o0, at = (o0 + r) >> 1;
+      for (size_t j = 0; j < len; ++j) {
+        unsigned const sh = (j & 1) ? 0u : 4u;
+        if (!packed_mode) bases4[at + (j >> 1)] |= static_cast<uint8_t>(BaseCode4(read_bases[o0 + j]) << sh);
+        if (q4) quals_packed[at + (j >> 1)] |= static_cast<uint8_t>(qcode[read_quals[o0 + j]] << sh);
+      }
+    }
+    packed.bases4 = bases4.data();
+    packed.quals = q4 ? quals_packed.data() : read_quals.data();
+    packed.qual_bits = q4 ? 4 : 8;
+    packed_view = view;
+    packed_view.read_bases = nullptr;
+    packed_view.read_quals = nullptr;
   }
 };
 
@@ -1131,7 +1219,7 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
         p = &arena.back();
       }
       n_reads += 1;
-      n_bases += a.seq.size();
+      n_bases += a.SeqLen();
       kept.push_back(Ref{p, HashQname(a.qname), name_prefix(a.qname), static_cast<uint32_t>(si), static_cast<uint32_t>(kept.size())});
     });
     double const bases_per_read = static_cast<double>(n_bases) / static_cast<double>(std::max<uint64_t>(n_reads, 1));
@@ -1149,7 +1237,7 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
       kept.resize(at);
     }
     uint64_t bases = 0;
-    for (size_t i = first; i < kept.size(); ++i) bases += kept[i].rec->seq.size();
+    for (size_t i = first; i < kept.size(); ++i) bases += kept[i].rec->SeqLen();
     sinfo.sampled_reads = sampled;
     sinfo.sampled_bases = bases;
     total_bases += bases;
@@ -1178,8 +1266,10 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
   for (auto const& sm : samples_) fb.sample_cov.back().push_back(static_cast<double>(sm.sampled_bases) / static_cast<double>(w.Length()));
   fb.ref_bases.insert(fb.ref_bases.end(), ref_seq.begin(), ref_seq.end());
   fb.ref_off.push_back(static_cast<uint32_t>(fb.ref_bases.size()));
-  size_t const nr = kept.size(), b0 = fb.read_bases.size(), r0 = fb.read_qname_id.size();
-  fb.read_bases.resize(b0 + total_bases);
+  size_t const nr = kept.size(), b0 = static_cast<size_t>(fb.read_off.back()), r0 = fb.read_qname_id.size();
+  bool const packed = prm_.packed_reads;
+  fb.packed_mode = packed;
+  if (!packed) fb.read_bases.resize(b0 + total_bases);
   fb.read_quals.resize(b0 + total_bases);
   fb.read_off.reserve(fb.read_off.size() + nr);
   fb.read_qname_id.resize(r0 + nr);
@@ -1195,12 +1285,24 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
   size_t at = b0;
   for (size_t i = 0; i < nr; ++i) {
     SamRecord const& a = *kept[i].rec;
-    std::memcpy(fb.read_bases.data() + at, a.seq.data(), a.seq.size());
+    size_t const len = a.SeqLen();
+    if (!packed) {
+      std::memcpy(fb.read_bases.data() + at, a.seq.data(), len);
+    } else if (a.packed) {  // a BAM record: its sequence bytes as they are
+      fb.seq4.insert(fb.seq4.end(), a.seq4.begin(), a.seq4.end());
+      fb.seq4_off.push_back(fb.seq4.size());
+    } else {                // SAM text: packed here
+      size_t const s0 = fb.seq4.size();
+      fb.seq4.resize(s0 + (len + 1) / 2, 0);
+      for (size_t x = 0; x < len; ++x)
+        fb.seq4[s0 + (x >> 1)] |= static_cast<uint8_t>(BaseCode4(static_cast<uint8_t>(a.seq[x])) << ((x & 1) ? 0 : 4));
+      fb.seq4_off.push_back(fb.seq4.size());
+    }
     uint8_t* q = fb.read_quals.data() + at;
-    size_t const nq = std::min(a.qual.size(), a.seq.size());  // (the arrays are sized by SEQ; the parsers reject a mismatch)
+    size_t const nq = std::min(a.qual.size(), len);  // (the arrays are sized by SEQ; the parsers reject a mismatch)
     for (size_t x = 0; x < nq; ++x) q[x] = a.qual[x] == 0xFF ? 0 : a.qual[x];
-    for (size_t x = nq; x < a.seq.size(); ++x) q[x] = 0;
-    at += a.seq.size();
+    for (size_t x = nq; x < len; ++x) q[x] = 0;
+    at += len;
     fb.read_off.push_back(at);
     size_t h = static_cast<size_t>(kept[i].qh * 0x9E3779B97F4A7C15ull >> 20) & (cap - 1);
     uint32_t id;
