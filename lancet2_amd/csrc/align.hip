@@ -73,7 +73,8 @@ struct AlnWs {
   // planning
   u32* win_slotmask;   // [n] bitmask of haplotype slots to align
   u32* win_case;       // [n] bitmask of the samples that have a CASE read in the window (k_plan_reads)
-  u64* pair_off;       // [n + 1]
+  ulonglong2* win_off; // [n + 1] x = pair_off: first global pair index of the window; y = ev_off: first slot of its evidence
+                       //         table (evidence.h) -- counted by k_plan, scanned together (k_scan_pairs), read as one 16-byte load
   u32* counters;       // [8]: 0 max read len, 1 max reads per window, 2 entries in vote_wg
   u32* vote_wg;        // [n * MH] compact list of (window * MH + slot) to align against
   u32* read_win;       // [n_reads] window of every read (k_read_planes writes it: no binary search per lane later)
@@ -82,7 +83,7 @@ struct AlnWs {
   // per pair
   i32* centre;         // [pairs in chunk] first diagonal of the pair's region (vmin - K), or a sentinel
   u32* band_w;         // [pairs in chunk] width of the region in diagonals | key << 16
-  u32* pair_read;      // [pairs in chunk] DP pairs only: read index | haplotype slot << 27 (no binary search over pair_off later)
+  u32* pair_read;      // [pairs in chunk] DP pairs only: read index | haplotype slot << 27 (no binary search over win_off later)
   u64* vote_aux;       // [pairs in chunk] wide pairs only: most-voted diagonal - region start | votes further than 8 / 16 / 24
                        //                  diagonals from it (saturating u16 each): k_align_wave's narrow first pass
   u32* dp_list;        // [pairs in chunk] pairs that need the DP (compacted by k_vote)
@@ -93,15 +94,14 @@ struct AlnWs {
   u32* gen_row;        // k_align_gen's (H,F) rows (HBM)
   u32 gen_w;           // widest region of this k_align_gen / k_align_wave launch
   unsigned long long* tbw;  // k_align_wave's traceback bit planes
-  // evidence table per window
-  u32 ev_cap;
-  u64* ev_key;         // [n][ev_cap]
-  u32* ev_min;         // [n][ev_cap]
+  // evidence table per window: window w owns the ev_slots() slots from win_off[w].y on (evidence.h)
+  u64* ev_key;         // [win_off[n].y]
+  u32* ev_min;         // [win_off[n].y]
   u8* asg_allele;      // [n_reads * MV] (internal copy when the caller passes NULL)
   uint2* ev_rec;       // [n_reads * MV] the winning assignment's hap_id, base_qual, own_nm, ref_nm (evidence.h); null unless the
                        //                call asked for the FORMAT statistics
   // alignment records, COMPACT: one per planned (read, haplotype) pair, indexed by the global pair index
-  // pair_off[w] + (rank of the haplotype slot among the window's aligned slots) * reads of the window + read -- the reads of
+  // win_off[w].x + (rank of the haplotype slot among the window's aligned slots) * reads of the window + read -- the reads of
   // one (window, haplotype) are consecutive, so a wavefront of k_assign (a lane per read) loads 64 records as one run.
   // (Round 4 kept them in the caller's fixed-stride layout [read][max_haps]: 1.5 KB between two lanes' records, 8 GB of
   //  workspace touched a sector at a time.)  The caller's debug taps aln_rec / aln_cigar are filled from these (k_tap_records).
@@ -186,7 +186,8 @@ __global__ void k_plan(GArgs A) {
     for (u32 mm = mask; mm; mm &= mm - 1) A.ws.vote_wg[at++] = static_cast<u32>(w) * P.max_haps + (__ffs(mm) - 1);
   }
   u32 const nr = A.b.read_win_off[w + 1] - A.b.read_win_off[w];
-  A.ws.pair_off[w] = static_cast<u64>(nr) * __popc(mask);  // counts; scanned below
+  // counts; scanned below (a window that is not genotyped files no evidence)
+  A.ws.win_off[w] = make_ulonglong2(static_cast<u64>(nr) * __popc(mask), mask ? ev_slots(nr, nv) : 0u);
   atomic_max_lazy(&A.ws.counters[1], nr);
 }
 
@@ -215,42 +216,49 @@ __global__ __launch_bounds__(256) void k_plan_reads(GArgs A) {
   }
 }
 
-__global__ void k_scan_pairs(u64* pair_off, int n) {  // single block exclusive scan (n <= few 100k)
-  __shared__ u64 carry;
-  __shared__ u64 sh[1024];
-  if (threadIdx.x == 0) carry = 0;
+__global__ void k_scan_pairs(ulonglong2* win_off, int n) {  // single block exclusive scan (n <= few 100k)
+  // the pairs and the evidence slots side by side: one pass, the same trips as the pairs alone took
+  __shared__ u64 carry[2];
+  __shared__ u64 sh[2][1024];
+  if (threadIdx.x < 2) carry[threadIdx.x] = 0;
   __syncthreads();
   for (int base = 0; base < n; base += 1024) {
     int const i = base + threadIdx.x;
-    u64 const v = i < n ? pair_off[i] : 0;
-    sh[threadIdx.x] = v;
+    ulonglong2 const v = i < n ? win_off[i] : make_ulonglong2(0, 0);
+    sh[0][threadIdx.x] = v.x;
+    sh[1][threadIdx.x] = v.y;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) {
-      u64 const x = threadIdx.x >= static_cast<u32>(d) ? sh[threadIdx.x - d] : 0;
+      bool const has = threadIdx.x >= static_cast<u32>(d);
+      u64 const x0 = has ? sh[0][threadIdx.x - d] : 0, x1 = has ? sh[1][threadIdx.x - d] : 0;
       __syncthreads();
-      sh[threadIdx.x] += x;
+      sh[0][threadIdx.x] += x0;
+      sh[1][threadIdx.x] += x1;
       __syncthreads();
     }
-    u64 const incl = sh[threadIdx.x];
-    if (i < n) pair_off[i] = carry + incl - v;
+    u64 const incl0 = sh[0][threadIdx.x], incl1 = sh[1][threadIdx.x];
+    if (i < n) win_off[i] = make_ulonglong2(carry[0] + incl0 - v.x, carry[1] + incl1 - v.y);
     __syncthreads();
-    if (threadIdx.x == 1023) carry += incl;
+    if (threadIdx.x == 1023) {
+      carry[0] += incl0;
+      carry[1] += incl1;
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) pair_off[n] = carry;
+  if (threadIdx.x == 0) win_off[n] = make_ulonglong2(carry[0], carry[1]);
 }
 
 // pair p -> (window, read, slot)
 struct PairId { int w; u32 r; u32 slot; };
 __device__ PairId pair_decode(GArgs const& A, u64 p) {
-  int lo = 0, hi = A.b.n_windows;  // largest w with pair_off[w] <= p
+  int lo = 0, hi = A.b.n_windows;  // largest w with win_off[w].x <= p
   while (hi - lo > 1) {
     int const mid = (lo + hi) / 2;
-    if (A.ws.pair_off[mid] <= p) lo = mid; else hi = mid;
+    if (A.ws.win_off[mid].x <= p) lo = mid; else hi = mid;
   }
   PairId id;
   id.w = lo;
-  u64 const local = p - A.ws.pair_off[lo];
+  u64 const local = p - A.ws.win_off[lo].x;
   u32 const nr = A.b.read_win_off[lo + 1] - A.b.read_win_off[lo];
   u32 const si = static_cast<u32>(local / nr);
   id.r = A.b.read_win_off[lo] + static_cast<u32>(local % nr);
@@ -544,7 +552,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
   u32 const mask = A.ws.win_slotmask[w];
   u32 const si = __popc(mask & ((1u << slot) - 1u));
   u32 const r0 = A.b.read_win_off[w], nr = A.b.read_win_off[w + 1] - r0;
-  u64 const p0 = A.ws.pair_off[w] + static_cast<u64>(si) * nr;  // global pair index of read 0
+  u64 const p0 = A.ws.win_off[w].x + static_cast<u64>(si) * nr;  // global pair index of read 0
   if (p0 + nr <= A.pair0 || p0 >= A.pair0 + A.npairs) return;
   // LDS is carved for the longest haplotype that is actually aligned in this batch (ml_eff), not for the capacity
   // max_hap_len: half the footprint on 1 kb windows, five workgroups per CU instead of three
@@ -2689,9 +2697,9 @@ __global__ __launch_bounds__(256) void k_ev_clear(GArgs A) {
   int const w = blockIdx.x;
   u32 const nv = A.v.win_nvars[w];
   if (nv == 0 || A.ws.win_slotmask[w] == 0) return;  // (k_assign / k_evidence leave at the same test)
-  u32 const cap = ev_slots(A.b.read_win_off[w + 1] - A.b.read_win_off[w], nv, A.ws.ev_cap);
-  u64* evk = A.ws.ev_key + static_cast<size_t>(w) * A.ws.ev_cap;
-  u32* evm = A.ws.ev_min + static_cast<size_t>(w) * A.ws.ev_cap;
+  u32 const cap = ev_slots(A.b.read_win_off[w + 1] - A.b.read_win_off[w], nv);
+  u64* evk = A.ws.ev_key + A.ws.win_off[w].y;  // (a multiple of 64 slots: 16-byte stores)
+  u32* evm = A.ws.ev_min + A.ws.win_off[w].y;
   for (u32 x = threadIdx.x; x < cap / 2; x += 256) reinterpret_cast<uint4*>(evk)[x] = make_uint4(0u, 0u, 0u, 0u);
   for (u32 x = threadIdx.x; x < cap / 4; x += 256) reinterpret_cast<uint4*>(evm)[x] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
 }
@@ -2724,18 +2732,19 @@ __global__ __launch_bounds__(64) void k_assign(GArgs A) {
     for (int v = 0; v < MV; ++v) A.o.asg_score[static_cast<size_t>(r) * MV + v] = 0.0;
   u32 const mask = A.ws.win_slotmask[w];
   if (nv == 0 || mask == 0) return;
-  // the records of this read: pair_off[w] + (rank of the haplotype's slot) * reads of the window + the read's place in it
+  // the records of this read: win_off[w].x + (rank of the haplotype's slot) * reads of the window + the read's place in it
   u32 const r0w = A.b.read_win_off[w], nrw = A.b.read_win_off[w + 1] - r0w;
-  u64 const gp_read = A.ws.pair_off[w] + (static_cast<u64>(r) - r0w);
+  ulonglong2 const wo = A.ws.win_off[w];
+  u64 const gp_read = wo.x + (static_cast<u64>(r) - r0w);
   u64 const ro = A.b.read_off[r];
   u32 const rlen = static_cast<u32>(A.b.read_off[r + 1] - ro);
   const u8* rb = A.b.read_bases + ro;
   const u8* rq = A.b.read_quals + ro;
   u32 sample = A.b.read_sample[r];
   u32 const qn = A.b.read_qname_id[r];
-  u64* evk = A.ws.ev_key + static_cast<size_t>(w) * A.ws.ev_cap;
-  u32* evm = A.ws.ev_min + static_cast<size_t>(w) * A.ws.ev_cap;
-  u32 const evmask = ev_slots(nrw, nv, A.ws.ev_cap) - 1;
+  u64* evk = A.ws.ev_key + wo.y;
+  u32* evm = A.ws.ev_min + wo.y;
+  u32 const evmask = ev_slots(nrw, nv) - 1;
 
   for (u32 c = 0; c < A.a.win_ncomp[w]; ++c) {
     size_t const ci = static_cast<size_t>(w) * P.max_comps + c;
@@ -2844,9 +2853,9 @@ __global__ __launch_bounds__(64) void k_evidence(GArgs A) {
   if (sample >= static_cast<u32>(S)) return;
   u32 const qn = A.b.read_qname_id[r];
   u32 const rev = (A.b.read_flags[r] & MA_RF_REV) ? 1u : 0u;
-  const u64* evk = A.ws.ev_key + static_cast<size_t>(w) * A.ws.ev_cap;
-  const u32* evm = A.ws.ev_min + static_cast<size_t>(w) * A.ws.ev_cap;
-  u32 const evmask = ev_slots(A.b.read_win_off[w + 1] - A.b.read_win_off[w], nv, A.ws.ev_cap) - 1;
+  const u64* evk = A.ws.ev_key + A.ws.win_off[w].y;
+  const u32* evm = A.ws.ev_min + A.ws.win_off[w].y;
+  u32 const evmask = ev_slots(A.b.read_win_off[w + 1] - A.b.read_win_off[w], nv) - 1;
   u32 const rloc = static_cast<u32>(r - A.b.read_win_off[w]);
   for (u32 v = 0; v < nv; ++v) {
     u32 const al = asg[v];
@@ -3018,9 +3027,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
   if (stats) A.f = *fmt;
   A.prm = P;
   AlnWs& ws = A.ws;
-  // evidence table: sized from the largest window (reads x a few variants each); the read count per
-  // window is known from read_win_off only on the device, so a first tiny pass fetches the maxima
-  ws.ev_cap = 8192;
+  // the read counts per window are known from read_win_off only on the device: a first tiny pass fetches the maxima
   u32 rwords_all = 8;  // words per read bit plane (longest read of the batch + two zero words)
   {
     MA_HIP(ctx, ctx->ws_misc.reserve(4096));
@@ -3030,16 +3037,11 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     u32 mr2[2] = {0, 0};
     MA_HIP(ctx, hipMemcpyAsync(mr2, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));
-    u32 const mr = mr2[0];
     rwords_all = (mr2[1] + 31) / 32 + 2;
     if (3u * rwords_all > 64u) {  // (cannot happen: k_max_reads leaves the windows with longer reads out)
       ma_set_err(ctx, "ma_genotype_batch: read planes do not fit a wavefront");
       return MA_ERR_PARAM;
     }
-    u64 want = static_cast<u64>(mr) * 8 + 1024;
-    u32 cap = 8192;
-    while (cap < want && cap < (1u << 24)) cap <<= 1;
-    ws.ev_cap = cap;
   }
 
   // fixed-size part of the workspace
@@ -3053,13 +3055,11 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     };
     ws.win_slotmask = reinterpret_cast<u32*>(take(4ull * n));
     ws.win_case = reinterpret_cast<u32*>(take(4ull * n));
-    ws.pair_off = reinterpret_cast<u64*>(take(8ull * (n + 1)));
+    ws.win_off = reinterpret_cast<ulonglong2*>(take(16ull * (n + 1)));
     ws.counters = reinterpret_cast<u32*>(take(64));
     ws.vote_wg = reinterpret_cast<u32*>(take(4ull * n * MH));
     ws.read_planes = reinterpret_cast<u32*>(take(4ull * NR * plane_stride(rwords_all) + 256));
     ws.read_win = reinterpret_cast<u32*>(take(4ull * NR + 64));
-    ws.ev_key = reinterpret_cast<u64*>(take(8ull * n * ws.ev_cap));
-    ws.ev_min = reinterpret_cast<u32*>(take(4ull * n * ws.ev_cap));
     ws.asg_allele = reinterpret_cast<u8*>(take(NR * MV + 16));
     ws.ev_rec = stats ? reinterpret_cast<uint2*>(take(8ull * NR * MV + 16)) : nullptr;
     return off;
@@ -3083,21 +3083,29 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
   ctx->tic("k_plan");
   hipLaunchKernelGGL(k_plan, dim3((n + 127) / 128), dim3(128), 0, ctx->stream, A);
   hipLaunchKernelGGL(k_plan_reads, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, A);
-  hipLaunchKernelGGL(k_ev_clear, dim3(n), dim3(256), 0, ctx->stream, A);  // (after k_plan: it reads the windows' slot masks)
-  hipLaunchKernelGGL(k_scan_pairs, dim3(1), dim3(1024), 0, ctx->stream, ws.pair_off, n);
+  hipLaunchKernelGGL(k_scan_pairs, dim3(1), dim3(1024), 0, ctx->stream, ws.win_off, n);
   ctx->toc();
-  u64 total_pairs = 0;
+  u64 totals[2] = {0, 0};  // pairs, evidence slots of the batch
   u32 plan_counters[4] = {0, 0, 0, 0};
-  MA_HIP(ctx, hipMemcpyAsync(&total_pairs, ws.pair_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+  MA_HIP(ctx, hipMemcpyAsync(totals, ws.win_off + n, 16, hipMemcpyDeviceToHost, ctx->stream));
   MA_HIP(ctx, hipMemcpyAsync(plan_counters, ws.counters, 16, hipMemcpyDeviceToHost, ctx->stream));
   MA_HIP(ctx, ma_stream_sync(ctx));
+  u64 const total_pairs = totals[0], ev_total = totals[1];
   u32 const max_read_len = plan_counters[0], n_vote_wg = plan_counters[2];
 
   ctx->stats[0] += total_pairs;
   // the compact alignment records: 32 bytes per planned pair (+ a side slot of 4 (1 + max_cigar) bytes that only DP pairs touch)
-  MA_HIP(ctx, ctx->ws_mm.reserve((total_pairs + 64) * (32ull + 4ull * (1 + MCG)) + 512));
+  // ... and behind them the evidence tables, every window's of its own size: 12 bytes per slot (key, lowest read)
+  size_t const rec_bytes = ((total_pairs + 64) * 32ull + 255ull) & ~255ull;
+  size_t const cig_bytes = ((total_pairs + 64) * 4ull * (1 + MCG) + 255ull) & ~255ull;
+  MA_HIP(ctx, ctx->ws_mm.reserve(rec_bytes + cig_bytes + 12ull * ev_total + 512));
   ws.rec = ctx->ws_mm.as<i32>();
-  ws.cig = reinterpret_cast<u32*>(reinterpret_cast<char*>(ctx->ws_mm.p) + (((total_pairs + 64) * 32ull + 255ull) & ~255ull));
+  ws.cig = reinterpret_cast<u32*>(reinterpret_cast<char*>(ctx->ws_mm.p) + rec_bytes);
+  ws.ev_key = reinterpret_cast<u64*>(reinterpret_cast<char*>(ctx->ws_mm.p) + rec_bytes + cig_bytes);
+  ws.ev_min = reinterpret_cast<u32*>(ws.ev_key + ev_total);
+  ctx->tic("k_plan");  // (its last part: the tables exist only now)
+  hipLaunchKernelGGL(k_ev_clear, dim3(n), dim3(256), 0, ctx->stream, A);
+  ctx->toc();
   if (total_pairs > 0) {
     ws.tb_rows = max_read_len + 1;
     // LDS of k_align_wave: two i32 rows of w + 2 cells, the haplotype codes of the region and the read's codes
@@ -3405,7 +3413,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     E.read_win_off = b.read_win_off; E.read_qname_id = b.read_qname_id; E.read_sample = b.read_sample;
     E.comp_nhaps = a.comp_nhaps;
     E.win_nvars = v.win_nvars; E.var_comp = v.var_comp; E.var_nalts = v.var_nalts; E.alt_length = v.alt_length;
-    E.win_slotmask = ws.win_slotmask; E.ev_key = ws.ev_key; E.ev_min = ws.ev_min; E.ev_cap = ws.ev_cap;
+    E.win_slotmask = ws.win_slotmask; E.win_off = ws.win_off; E.ev_key = ws.ev_key; E.ev_min = ws.ev_min;
     E.asg_allele = ws.asg_allele; E.ev_rec = ws.ev_rec;
     E.allele_counts = A.o.allele_counts;
     E.o = A.f;

@@ -10,15 +10,18 @@ __device__ __forceinline__ u64 ev_key_of(u32 var, u32 sample, u32 allele, u32 qn
           (static_cast<u64>(qname) << 1)) + 1ull;
 }
 
-// The evidence table of a window: [ev_cap] slots are reserved for every window (the largest one sizes them), a window uses
-// the first ev_slots() of its own -- a power of two holding 1.5 x (its reads x its variants) keys, every read files at most
-// one key per variant -- and only those are cleared per batch: 1-2 k of the 8 k slots on the whole-genome workload (the two
-// whole-array memsets were 1.6 GB per step of 16384 windows, 2.3 ms of fill kernels).
-__device__ __forceinline__ u32 ev_slots(u32 nrw, u32 nv, u32 cap_max) {
+// The evidence table of a window: ev_slots() slots of its own -- a power of two, at least 64, that holds 1.5 x (its reads x
+// its variants) keys; every read files at most one key per variant, so the table never fills and a probe always ends at a
+// free slot.  The tables lie one behind the other: window w's begins at slot win_off[w].y, an exclusive scan of ev_slots() over
+// the genotyped windows (k_plan, k_scan_pairs; align.hip), and k_assign, k_evidence, k_ev_clear and k_evid_stats all size
+// and place it through this one function.  1-4 k slots per window on the whole-genome workload, where a fixed 8192 per
+// window used to be reserved -- and a window of 160 reads x 60 variants lost the depths that did not fit them.
+// (the reads of a window are bounded by k_vote's LDS, a few ten thousand: times max_vars <= 128 the count is far below 2^31)
+__device__ __forceinline__ u32 ev_slots(u32 nrw, u32 nv) {
   u64 const need = static_cast<u64>(nrw) * nv * 3u / 2u + 16u;
-  if (need >= cap_max) return cap_max;
+  if (need > (1ull << 31)) return 1u << 31;
   u32 const c = 1u << (32 - __builtin_clz(static_cast<u32>(need) - 1u));
-  return min(max(c, 64u), cap_max);
+  return max(c, 64u);
 }
 
 // The winning assignment of a read at a variant, beside its allele (asg_allele): 8 bytes per (read, variant slot), written by
@@ -45,9 +48,9 @@ struct EvStatArgs {
   const i32* alt_length;
   // the genotype stage's own
   const u32* win_slotmask;
+  const ulonglong2* win_off;  // [n + 1] .y: first slot of every window's table
   const u64* ev_key;
   const u32* ev_min;
-  u32 ev_cap;
   const u8* asg_allele;     // [n_reads * max_vars]
   const uint2* ev_rec;      // [n_reads * max_vars]
   const u32* allele_counts;

@@ -62,9 +62,9 @@ __global__ __launch_bounds__(kEvThreads) void k_evid_stats(EvStatArgs A) {
   int const K = min(static_cast<int>(A.var_nalts[vi]) + 1, NA);
   u32 const nhaps = A.comp_nhaps[static_cast<size_t>(w) * P.max_comps + A.var_comp[vi]];
   u32 const r0 = A.read_win_off[w], nrw = A.read_win_off[w + 1] - r0;
-  const u64* evk = A.ev_key + static_cast<size_t>(w) * A.ev_cap;
-  const u32* evm = A.ev_min + static_cast<size_t>(w) * A.ev_cap;
-  u32 const evmask = ev_slots(nrw, nv, A.ev_cap) - 1;
+  const u64* evk = A.ev_key + A.win_off[w].y;
+  const u32* evm = A.ev_min + A.win_off[w].y;
+  u32 const evmask = ev_slots(nrw, nv) - 1;
   f64 max_var_len = 0.0;  // variant_call.cpp:179-182: the longest |AltAllele::mLength| of the variant
   for (int a = 0; a + 1 < K; ++a) max_var_len = fmax(max_var_len, fabs(static_cast<f64>(A.alt_length[vi * MA + a])));
   // this thread's bin: the error probability of its quality and the two logs NPBQ adds up

@@ -286,6 +286,65 @@ def handmade_annotation_case(p, cases):
     return asm, var
 
 
+def handmade_genotype_case(p, windows):
+    """handmade_annotation_case's sibling for the genotype stage: several components and variants per window.
+    window = dict(comps=[[ref, alt1, ...], ...] (byte strings; the haplotype slots are numbered through the components in
+                  order, comp_hap0 = the haplotypes before),
+                  vars=[dict(comp, ref_start, ref_len, alts=[(alt_len, {haplotype within its component: start})...])...])
+    The allele pool holds the REF allele cut from the component's first haplotype and every ALT allele cut from the first
+    haplotype that carries it; alt_length = alt_len - ref_len (1 for a substitution)."""
+    n = len(windows)
+    asm = capi.alloc_host(capi.asm_out_spec(p, n))
+    var = capi.alloc_host(capi.var_out_spec(p, n))
+    MC, MH, ML, MV, MA, MP = p.max_comps, p.max_haps, p.max_hap_len, p.max_vars, p.max_alts, p.max_allele_bytes
+    for w, win in enumerate(windows):
+        comps = win["comps"]
+        assert len(comps) <= MC and sum(len(c) for c in comps) <= MH and len(win["vars"]) <= MV
+        asm["win_ncomp"][w] = len(comps)
+        asm["win_k"][w] = 25
+        hap0 = 0
+        for c, haps in enumerate(comps):
+            ci = w * MC + c
+            asm["comp_hap0"][ci] = hap0
+            asm["comp_nhaps"][ci] = len(haps)
+            asm["comp_cx"][ci * 3:ci * 3 + 3] = (3, 2, 2)
+            asm["comp_cxf"][ci * 4:ci * 4 + 4] = (0.5, 0.25, 0.125, 0.0)
+            for h, seq in enumerate(haps):
+                hi = w * MH + hap0 + h
+                assert len(seq) <= ML
+                asm["hap_len"][hi] = len(seq)
+                asm["hap_bases"][hi * ML:hi * ML + len(seq)] = np.frombuffer(bytes(seq), np.uint8)
+            hap0 += len(haps)
+        var["win_nvars"][w] = len(win["vars"])
+        pool = 0
+        pl = var["allele_pool"][w * MP:(w + 1) * MP]
+        for v, vs in enumerate(win["vars"]):
+            vi = w * MV + v
+            haps = comps[vs["comp"]]
+            assert 1 <= len(vs["alts"]) <= MA
+            var["var_comp"][vi] = vs["comp"]
+            var["var_pos"][vi] = vs["ref_start"] + 1
+            var["var_ref_start"][vi] = vs["ref_start"]
+            var["var_ref_len"][vi] = vs["ref_len"]
+            var["var_ref_off"][vi] = pool
+            pl[pool:pool + vs["ref_len"]] = np.frombuffer(bytes(haps[0][vs["ref_start"]:vs["ref_start"] + vs["ref_len"]]), np.uint8)
+            pool += vs["ref_len"]
+            var["var_nalts"][vi] = len(vs["alts"])
+            var["var_hap_start"][vi * MH] = vs["ref_start"]
+            for ai, (alen, sites) in enumerate(vs["alts"]):
+                h1, s1 = sorted(sites.items())[0]
+                var["alt_off"][vi * MA + ai] = pool
+                var["alt_len"][vi * MA + ai] = alen
+                var["alt_length"][vi * MA + ai] = (alen - vs["ref_len"]) if alen != vs["ref_len"] else 1
+                pl[pool:pool + alen] = np.frombuffer(bytes(haps[h1][s1:s1 + alen]), np.uint8)
+                pool += alen
+                for h, st in sites.items():
+                    assert 1 <= h < len(haps)
+                    var["var_hap_allele"][vi * MH + h] = ai + 1
+                    var["var_hap_start"][vi * MH + h] = st
+        assert pool <= MP
+    return asm, var
+
 
 class DeviceArena:
     """hipMalloc / hipMemcpy through ctypes on the HIP runtime the product library is using (no torch import: the
