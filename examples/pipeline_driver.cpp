@@ -6,6 +6,8 @@
 //             are left are flattened into batches
 //   engine    ma_prefetch_batch(next) + ma_process_batch(this) (ma_process_stats_batch with --out-vcf): the next batch uploads under this batch's kernels
 //             (--packed-reads: the ma_*_packed_batch pair on 4-bit read bases and qualities, half the bytes over the link)
+//             (--read-meta with --out-vcf: ma_prefetch_meta_batch + ma_process_meta_batch on the reads' MAPQ, clip and pair flags,
+//              insert size and start -- RMQ, SCA, FLD, RPCD, MQCD, FSSE are printed too: 24 of 24 FORMAT values)
 //   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
 // Build (no HIP headers needed; zlib only for BAM input):
@@ -43,7 +45,9 @@ struct Outputs {  // caller-owned fixed-stride result buffers of one batch
   std::vector<double> cx_d;
   ma_fmt_out_t fmt{};  // read-level FORMAT statistics: asked for with --out-vcf only
   std::vector<double> fmt_d;
-  void Allocate(const ma_params_t& p, int n, bool with_stats) {
+  ma_fmt_meta_out_t fmeta{};  // RMQ and SCA / FLD / RPCD / MQCD / FSSE: asked for with --out-vcf --read-meta only
+  std::vector<double> fmeta_d;
+  void Allocate(const ma_params_t& p, int n, bool with_stats, bool with_meta = false) {
     size_t const N = n, MC = p.max_comps, MH = p.max_haps, ML = p.max_hap_len, MR = p.max_runs, MV = p.max_vars, MA = p.max_alts,
                  MP = p.max_allele_bytes, S = p.num_samples;
     size_t const G = (MA + 1) * (MA + 2) / 2;
@@ -82,6 +86,11 @@ struct Outputs {  // caller-owned fixed-stride result buffers of one batch
       fmt.fmt_npbq = fmt_d.data();
       fmt.fmt_cmlod = fmt.fmt_npbq + N * MV * S * (MA + 1);
       fmt.fmt_stat = fmt.fmt_cmlod + N * MV * S * MA;
+    }
+    if (with_meta) {  // (the integer tallies ev_meta / ev_rpcd are not needed for the VCF)
+      fmeta_d.assign(N * MV * S * ((MA + 1) + 5), 0.0);
+      fmeta.fmt_rmq = fmeta_d.data();
+      fmeta.fmt_mstat = fmeta.fmt_rmq + N * MV * S * (MA + 1);
     }
   }
 };
@@ -151,6 +160,10 @@ void DumpBatch(const std::string& dir, FlatBatch const& fb) {
   put("read_sample.u8", fb.read_sample.data(), fb.read_sample.size());
   put("read_flags.u8", fb.read_flags.data(), fb.read_flags.size());
   put("read_hint.i32", fb.read_hint.data(), 4 * fb.read_hint.size());
+  put("read_mapq.u8", fb.read_mapq.data(), fb.read_mapq.size());  // the read metadata of ma_read_meta_t
+  put("read_mflags.u8", fb.read_mflags.data(), fb.read_mflags.size());
+  put("read_isize.i32", fb.read_isize.data(), 4 * fb.read_isize.size());
+  put("read_start.i32", fb.read_start.data(), 4 * fb.read_start.size());
   std::vector<uint64_t> wins;
   for (auto const& w : fb.windows) {
     wins.push_back(static_cast<uint64_t>(w.chrom));
@@ -199,7 +212,7 @@ int main(int argc, char** argv) {
   ReadCollector::Params rp;
   ma_params_t prm;
   ma_default_params(&prm);
-  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false;
+  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false;
   int batch_windows = 512;
   int extract_threads = static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
   for (int i = 1; i < argc; ++i) {
@@ -229,6 +242,7 @@ int main(int argc, char** argv) {
     else if (a == "--dump") dump_dir = next();
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
+    else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
     else if (a == "--extract-only") extract_only = true;  // stage 1 alone (with --dump): no device needed
     else { std::fprintf(stderr, "pipeline_driver: unknown option %s\n", a.c_str()); return 2; }
   }
@@ -237,7 +251,10 @@ int main(int argc, char** argv) {
                          "  --packed-reads  read bases (and <= 16 distinct qualities per batch) go to the engine as 4-bit codes: a BAM record's\n"
                          "                  sequence bytes are copied undecoded, SAM text is packed.  A base letter that is none of BAM's\n"
                          "                  =ACMGRSVTWYHKDBN (lower case included) becomes N, as in a BAM file; without the flag it is passed on\n"
-                         "                  as it is.  Not with --collect-reads / --extract-pairs\n");
+                         "                  as it is.  Not with --collect-reads / --extract-pairs\n"
+                         "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
+                         "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
+                         "                  all 24 FORMAT values.  Without it those six are \".\"\n");
     return 2;
   }
   if (packed_reads && (collect_reads || rp.extract_pairs)) {
@@ -522,6 +539,7 @@ int main(int argc, char** argv) {
     to_engine.Close();
   });
   // ---- stage 2: engine ----
+  bool const with_meta = read_meta && !vcf_path.empty();
   std::thread engine([&] {
     Job j;
     while (to_engine.Pop(&j)) {
@@ -531,14 +549,19 @@ int main(int argc, char** argv) {
       }
       Job* nxt = nullptr;
       if (to_engine.Peek(&nxt)) {  // uploads under this batch's kernels
-        if (packed_reads) ma_prefetch_packed_batch(ctx, &nxt->batch->packed_view, &nxt->batch->packed);
+        if (with_meta) ma_prefetch_meta_batch(ctx, packed_reads ? &nxt->batch->packed_view : &nxt->batch->view,
+                                              packed_reads ? &nxt->batch->packed : nullptr, &nxt->batch->meta);
+        else if (packed_reads) ma_prefetch_packed_batch(ctx, &nxt->batch->packed_view, &nxt->batch->packed);
         else ma_prefetch_batch(ctx, &nxt->batch->view);
       }
       auto const t0 = Clock::now();
       j.out = std::make_unique<Outputs>();
-      j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty());
+      j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty(), with_meta);
       const ma_fmt_out_t* fmt = vcf_path.empty() ? nullptr : &j.out->fmt;  // (null: ma_process_batch)
-      j.rc = packed_reads ? ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb,
+      j.rc = with_meta ? ma_process_meta_batch(ctx, packed_reads ? &j.batch->packed_view : &j.batch->view,
+                                               packed_reads ? &j.batch->packed : nullptr, &j.batch->meta, &j.out->gate, &j.out->asmb,
+                                               &j.out->vars, &j.out->geno, fmt, &j.out->fmeta)
+             : packed_reads ? ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb,
                                                     &j.out->vars, &j.out->geno, fmt)
                           : ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, fmt);
       if (j.rc == MA_OK && !vcf_path.empty())  // INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
@@ -579,7 +602,8 @@ int main(int argc, char** argv) {
       // window order here; windows the gates skipped count as done)
       auto const tf = Clock::now();
       store.AddVariants(RecordsOfBatch(prm, *j.batch, j.out->vars, j.out->geno, as_vcf ? &j.out->cx : nullptr, true,
-                                       as_vcf ? &j.out->fmt : nullptr, as_vcf ? &j.out->asmb : nullptr));
+                                       as_vcf ? &j.out->fmt : nullptr, as_vcf ? &j.out->asmb : nullptr,
+                                       as_vcf && read_meta ? &j.out->fmeta : nullptr));
       size_t const done_upto = j.batch->windows.back().genome_index + 1;
       constexpr size_t kBufferWindows = 100;
       if (done_upto > kBufferWindows && done_upto - kBufferWindows > idx_to_flush) {

@@ -16,6 +16,9 @@
  *                             (caller/variant_support.h:361-411, caller/variant_call.cpp:141-196, :347-381)
  *   ma_process_packed_batch / ma_prefetch_packed_batch: ma_process_stats_batch / ma_prefetch_batch with the read bases, and
  *                             optionally the qualities, as 4-bit codes (ma_packed_reads_t): half the bytes over the link
+ *   ma_genotype_meta_batch / ma_process_meta_batch / ma_prefetch_meta_batch: the calls above + four facts of every read's BAM
+ *                             record (ma_read_meta_t) and the six FORMAT statistics over them: RMQ, MQCD, SCA, FLD, RPCD, FSSE
+ *                             (caller/variant_support.cpp:184-194, :261-305, :358-363, base/mann_whitney.h:127-225)
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -243,6 +246,35 @@ typedef struct ma_packed_reads {
   uint8_t qual_dict[16];   /* Phred value of each 4-bit code (qual_bits == 4) */
 } ma_packed_reads_t;
 
+/* ---- read metadata and the six FORMAT statistics over it ----------------------------------------------------------- */
+/* RMQ, MQCD, SCA, FLD, RPCD and FSSE of every (window, variant slot, sample), over the same de-duplicated evidence reads as
+ * ma_fmt_out_t (of mates that share a name, support one allele and belong to one sample only the first counts, with ITS
+ * metadata).  Four facts per read come from the caller's BAM record; the fifth input, the position of the variant in the
+ * read, is taken from the alignment that won AssignReadToAlleles (caller/combined_scorer.cpp:96-105). */
+enum ma_read_mflags { MA_RM_SOFTCLIP = 1u << 0,   /* cbdg::Read::IsSoftClipped(): soft-clipped bases >= 6 % of the read (cbdg/read.h:39-50) */
+                      MA_RM_PROPER = 1u << 1 };   /* SAM flag 0x2 (cbdg/read.h:72) */
+typedef struct ma_read_meta {      /* every member [n_reads], all four required */
+  const uint8_t* read_mapq;        /* cbdg::Read::MapQual() */
+  const uint8_t* read_mflags;      /* MA_RM_* */
+  const int32_t* read_isize;       /* InsertSize(): BAM tlen, signed */
+  const int32_t* read_start;       /* StartPos0(): BAM pos, >= 0 */
+} ma_read_meta_t;
+/* Every member optional (may be NULL); a cell is a (window, variant slot, sample), laid out like ma_fmt_out_t.  Unused variant
+ * slots and samples without evidence hold zeros (fmt_mstat: NaN).  ALT = the ALT alleles pooled.
+ *   ev_meta  per allele: sum of mapq^2, soft-clipped reads, proper-pair reads with isize != 0, sum of their isize
+ *   ev_rpcd  n_ref, n_alt, 2 x the ALT mid-rank sum, sum of t^3 - t over the tie groups -- of the folded positions
+ *            min(x, 1.0 - x), x = (double)qpos / (double)read length, ranked as the doubles they are (bit patterns)
+ *   fmt_rmq  RMQ per allele (caller/variant_support.cpp:184-194); 0.0 for an allele without reads
+ *   fmt_mstat SCA (variant_support.cpp:261-279), FLD (:49-51, variant_support.h:361-387), RPCD, MQCD (base/mann_whitney.h:
+ *            127-225), FSSE (variant_support.h:391-411, .cpp:358-363); NaN = missing (the reference's nullopt): FLD when REF
+ *            or ALT has no insert size, RPCD / MQCD when REF or ALT has no read, FSSE below three ALT reads */
+typedef struct ma_fmt_meta_out {
+  int64_t* ev_meta;    /* [n * max_vars * S * (max_alts+1) * 4] */
+  uint64_t* ev_rpcd;   /* [n * max_vars * S * 4] */
+  double* fmt_rmq;     /* [n * max_vars * S * (max_alts+1)] */
+  double* fmt_mstat;   /* [n * max_vars * S * 5] */
+} ma_fmt_meta_out_t;
+
 typedef struct ma_ctx ma_ctx_t;
 
 int ma_create(const ma_params_t* prm, int device, int memspace, ma_ctx_t** out);
@@ -305,6 +337,29 @@ int ma_process_packed_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_
                             const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno,
                             const ma_fmt_out_t* fmt);
 int ma_prefetch_packed_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* next_pk);
+
+/* ma_genotype_stats_batch / ma_process_stats_batch / ma_process_packed_batch (pk != NULL) / the two prefetch calls + the
+ * read metadata and the statistics over it.  fmeta == NULL, or all four members NULL, IS the call without them -- the same
+ * kernels, nothing allocated, and `meta` is not read.  Any member of fmeta set with meta NULL, or with a NULL member of meta,
+ * is MA_ERR_ARG.  Both memory spaces: with MA_MEM_DEVICE meta's four arrays are device pointers (the structs themselves are
+ * always in host memory).  The genotype stage then notes the variant's position in the winning alignment in the record it
+ * keeps per read and variant slot, and k_evid_stats tallies the metadata of the evidence reads and ranks their positions (one
+ * sort per cell).  A prefetched batch is recognised by the batch's address, its counts, pk's address AND
+ * meta's: one queued by ma_prefetch_batch / ma_prefetch_packed_batch and brought here with statistics wanted, or queued with
+ * another meta, is dropped and computed in the call; a call that does not ask for the statistics takes a queued batch whatever
+ * metadata came with it.  meta and its arrays stay unchanged as long as `next` must.
+ * Workspace: a cell's keys are sorted in LDS up to 2048 of them (evidence reads + ALT reads); only windows of more than 1024
+ * reads get a sort slice in device memory, 16 bytes x the next power of two of twice the window's reads per variant of the
+ * window (a deep-panel window of 7000 reads: 256 KB per variant; 2048 such windows of three variants: 1.6 GB). */
+int ma_genotype_meta_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_read_meta_t* meta, const ma_asm_out_t* asmb,
+                           const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt,
+                           const ma_fmt_meta_out_t* fmeta);
+int ma_process_meta_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk /* NULL: an ASCII batch */,
+                          const ma_read_meta_t* meta, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
+                          const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt,
+                          const ma_fmt_meta_out_t* fmeta);
+int ma_prefetch_meta_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* next_pk /* or NULL */,
+                           const ma_read_meta_t* next_meta);
 
 /* Kernel timing mode: 0 = off, 1 = reset at every API call (default), 2 = accumulate across calls
  * until ma_timing_control is called again (used by bench.py to time kernels over the timed region), 3 = as 2 and

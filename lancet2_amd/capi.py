@@ -69,6 +69,22 @@ class FmtOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ev_sums", "fmt_npbq", "fmt_cmlod", "fmt_stat")]
 
 
+MA_RM_SOFTCLIP, MA_RM_PROPER = 1, 2
+
+
+class ReadMeta(C.Structure):
+    """ma_read_meta_t: four per-read arrays, all required"""
+    _fields_ = [(n, C.c_void_p) for n in ("read_mapq", "read_mflags", "read_isize", "read_start")]
+
+
+class FmtMetaOut(C.Structure):
+    """ma_fmt_meta_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in ("ev_meta", "ev_rpcd", "fmt_rmq", "fmt_mstat")]
+
+
+META_DTYPES = dict(read_mapq=np.uint8, read_mflags=np.uint8, read_isize=np.int32, read_start=np.int32)
+
+
 class PackedReads(C.Structure):
     """ma_packed_reads_t"""
     _fields_ = [("bases4", C.c_void_p), ("quals", C.c_void_p), ("qual_bits", C.c_int32), ("qual_dict", C.c_uint8 * 16)]
@@ -139,6 +155,15 @@ def fmt_out_spec(p, n):
     MV, MA, S = p.max_vars, p.max_alts, p.num_samples
     return dict(ev_sums=(np.uint32, n * MV * S * (MA + 1) * 3), fmt_npbq=(np.float64, n * MV * S * (MA + 1)),
                 fmt_cmlod=(np.float64, n * MV * S * MA), fmt_stat=(np.float64, n * MV * S * 4))
+
+
+def fmt_meta_out_spec(p, n):
+    """the statistics over the read metadata (ma_genotype_meta_batch / ma_process_meta_batch); ev_meta per allele: sum of
+    mapq^2, soft-clipped reads, proper pairs with an insert size, sum of their insert sizes; ev_rpcd: n_ref, n_alt, 2 x the ALT
+    mid-rank sum, tie term; fmt_mstat: SCA, FLD, RPCD, MQCD, FSSE"""
+    MV, MA, S = p.max_vars, p.max_alts, p.num_samples
+    return dict(ev_meta=(np.int64, n * MV * S * (MA + 1) * 4), ev_rpcd=(np.uint64, n * MV * S * 4),
+                fmt_rmq=(np.float64, n * MV * S * (MA + 1)), fmt_mstat=(np.float64, n * MV * S * 5))
 
 
 def cx_out_spec(p, n):

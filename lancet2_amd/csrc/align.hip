@@ -100,6 +100,7 @@ struct AlnWs {
   u8* asg_allele;      // [n_reads * MV] (internal copy when the caller passes NULL)
   uint2* ev_rec;       // [n_reads * MV] the winning assignment's hap_id, base_qual, own_nm, ref_nm (evidence.h); null unless the
                        //                call asked for the FORMAT statistics
+  u32 ev_qpos;         // the call asked for the statistics over the read metadata: ev_rec also holds the variant's position in the read
   // alignment records, COMPACT: one per planned (read, haplotype) pair, indexed by the global pair index
   // win_off[w].x + (rank of the haplotype slot among the window's aligned slots) * reads of the window + read -- the reads of
   // one (window, haplotype) are consecutive, so a wavefront of k_assign (a lane per read) loads 64 records as one run.
@@ -2758,6 +2759,7 @@ __global__ __launch_bounds__(64) void k_assign(GArgs A) {
       bool have_best = false;
       Scored bestsc{};
       u32 best_h = 0, best_bq = 255;
+      i32 best_vstart = 0;
       for (u32 h = 0; h < nh; ++h) {  // alignments in haplotype order (all_alns)
         u64 const gp = gp_read + static_cast<u64>(__popc(mask & ((1u << (hap0 + h)) - 1u))) * nrw;
         if (!(mask & (1u << (hap0 + h)))) continue;  // (not aligned: no record)
@@ -2793,6 +2795,7 @@ __global__ __launch_bounds__(64) void k_assign(GArgs A) {
         if constexpr (kStats) {
           best_h = h;
           best_bq = bq;
+          best_vstart = vstart;
         }
       }
       if (!have_best) continue;
@@ -2814,7 +2817,16 @@ __global__ __launch_bounds__(64) void k_assign(GArgs A) {
         }
         // (the winner overlaps the variant, so rs < re: nm_of never answers the read length for it)
         u32 const own_nm = best_h == 0 ? ref_nm : nm_of(best_h);
-        A.ws.ev_rec[static_cast<size_t>(r) * MV + v] = ev_rec_pack(best_h, best_bq == 255 ? 0u : best_bq, own_nm, ref_nm);
+        u32 qpos = 0;
+        if (A.ws.ev_qpos) {  // the folded read position's numerator (combined_scorer.cpp:96-105), on the winning alignment
+          u64 const gp = gp_read + static_cast<u64>(__popc(mask & ((1u << (hap0 + best_h)) - 1u))) * nrw;
+          const u32* rp = rec_at(A.ws, gp);
+          uint4 const ah = *reinterpret_cast<const uint4*>(rp);
+          Cig cg{ah.w <= 4u ? rp + 4 : cig_at(A.ws, A.prm, gp) + 1, min(ah.w, static_cast<u32>(MCG))};
+          i32 const rs = static_cast<i32>(ah.y & 0xFFFFu);
+          qpos = refpos_to_qpos(cg, static_cast<u32>(max(0, best_vstart - rs)));
+        }
+        A.ws.ev_rec[static_cast<size_t>(r) * MV + v] = ev_rec_pack(best_h, best_bq == 255 ? 0u : best_bq, own_nm, ref_nm, qpos);
       }
       asg[v] = static_cast<u8>(bestsc.allele);
       if (A.o.asg_allele) A.o.asg_allele[static_cast<size_t>(r) * MV + v] = static_cast<u8>(bestsc.allele);
@@ -3008,7 +3020,7 @@ __global__ __launch_bounds__(256) void k_qual(GArgs A) {
 }  // namespace
 
 int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& v,
-                    const ma_geno_out_t& o_in, const ma_fmt_out_t* fmt) {
+                    const ma_geno_out_t& o_in, const ma_fmt_out_t* fmt, const ma_fmt_meta_out_t* fmeta) {
   int const n = b.n_windows;
   if (n == 0) return MA_OK;
   ma_params_t const& P = ctx->prm;
@@ -3023,12 +3035,14 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
   A.a = a;
   A.v = v;
   A.o = o_in;
-  bool const stats = fmt && fmt_wanted(*fmt);
-  if (stats) A.f = *fmt;
+  bool const meta = fmeta && fmeta_wanted(*fmeta);  // (api.hip has checked that the batch brings the four arrays)
+  bool const stats = (fmt && fmt_wanted(*fmt)) || meta;
+  if (fmt && fmt_wanted(*fmt)) A.f = *fmt;
   A.prm = P;
   AlnWs& ws = A.ws;
   // the read counts per window are known from read_win_off only on the device: a first tiny pass fetches the maxima
   u32 rwords_all = 8;  // words per read bit plane (longest read of the batch + two zero words)
+  u32 max_win_reads = 0;
   {
     MA_HIP(ctx, ctx->ws_misc.reserve(4096));
     u32* cnt = ctx->ws_misc.as<u32>();
@@ -3038,6 +3052,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     MA_HIP(ctx, hipMemcpyAsync(mr2, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));
     rwords_all = (mr2[1] + 31) / 32 + 2;
+    max_win_reads = mr2[0];
     if (3u * rwords_all > 64u) {  // (cannot happen: k_max_reads leaves the windows with longer reads out)
       ma_set_err(ctx, "ma_genotype_batch: read planes do not fit a wavefront");
       return MA_ERR_PARAM;
@@ -3067,6 +3082,7 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
   size_t const fixed = carve_fixed(nullptr);
   MA_HIP(ctx, ctx->ws_aln.reserve(fixed + 4096));
   carve_fixed(static_cast<char*>(ctx->ws_aln.p));
+  ws.ev_qpos = meta ? 1u : 0u;
   MA_HIP(ctx, hipMemsetAsync(ws.counters, 0, 64, ctx->stream));
   MA_HIP(ctx, hipMemsetAsync(A.o.allele_counts, 0,
                              4ull * n * MV * P.num_samples * (P.max_alts + 1) * 2, ctx->stream));
@@ -3417,7 +3433,12 @@ int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const m
     E.asg_allele = ws.asg_allele; E.ev_rec = ws.ev_rec;
     E.allele_counts = A.o.allele_counts;
     E.o = A.f;
-    MA_TRY_RC(launch_evid_stats(ctx, E));
+    if (meta) {
+      E.read_off = b.read_off;
+      E.read_mapq = b.read_mapq; E.read_mflags = b.read_mflags; E.read_isize = b.read_isize; E.read_start = b.read_start;
+      E.m = *fmeta;
+    }
+    MA_TRY_RC(launch_evid_stats(ctx, E, max_win_reads));
   }
   MA_HIP(ctx, hipGetLastError());
   return MA_OK;

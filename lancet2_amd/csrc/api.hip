@@ -90,6 +90,12 @@ std::vector<OutField> fmt_fields(const ma_params_t& p, int n) {
           {off_of(&ma_fmt_out_t::fmt_cmlod), 8 * N * MV * S * MA}, {off_of(&ma_fmt_out_t::fmt_stat), 8 * N * MV * S * 4}};
 }
 
+std::vector<OutField> fmeta_fields(const ma_params_t& p, int n) {
+  size_t const N = n, MV = p.max_vars, MA = p.max_alts, S = p.num_samples;
+  return {{off_of(&ma_fmt_meta_out_t::ev_meta), 8 * N * MV * S * (MA + 1) * 4}, {off_of(&ma_fmt_meta_out_t::ev_rpcd), 8 * N * MV * S * 4},
+          {off_of(&ma_fmt_meta_out_t::fmt_rmq), 8 * N * MV * S * (MA + 1)}, {off_of(&ma_fmt_meta_out_t::fmt_mstat), 8 * N * MV * S * 5}};
+}
+
 std::vector<OutField> cx_fields(const ma_params_t& p, int n) {
   size_t const N = n, MV = p.max_vars;
   return {{off_of(&ma_cx_out_t::seq_cx_i), 4 * N * MV * 4}, {off_of(&ma_cx_out_t::seq_cx_f), 4 * N * MV * 4},
@@ -141,11 +147,17 @@ struct OutMirror {
   }
 };
 
-int stage_batch(ma_ctx* ctx, const ma_batch_t* b, DBatch* d) {
+int stage_batch(ma_ctx* ctx, const ma_batch_t* b, DBatch* d, const ma_read_meta_t* meta = nullptr) {
   if (!b || b->n_windows < 0 || b->n_reads < 0) return MA_ERR_ARG;
   d->n_windows = b->n_windows;
   d->n_reads = b->n_reads;
+  d->read_mapq = d->read_mflags = nullptr;
+  d->read_isize = d->read_start = nullptr;
   if (ctx->memspace == MA_MEM_DEVICE) {
+    if (meta) {
+      d->read_mapq = meta->read_mapq; d->read_mflags = meta->read_mflags;
+      d->read_isize = meta->read_isize; d->read_start = meta->read_start;
+    }
     d->ref_bases = b->ref_bases; d->ref_off = b->ref_off; d->read_win_off = b->read_win_off;
     d->read_off = b->read_off; d->read_bases = b->read_bases; d->read_quals = b->read_quals;
     d->read_qname_id = b->read_qname_id; d->read_sample = b->read_sample; d->read_flags = b->read_flags;
@@ -176,6 +188,19 @@ int stage_batch(ma_ctx* ctx, const ma_batch_t* b, DBatch* d) {
     if (items[i].pad)
       MA_HIP(ctx, hipMemsetAsync(static_cast<char*>(ctx->in_stage[i].p) + items[i].bytes, 0, items[i].pad, ctx->stream));
     *items[i].dst = ctx->in_stage[i].p;
+  }
+  if (meta) {  // the read metadata, like read_hint: four more per-read arrays
+    struct Meta { const void* src; size_t bytes; const void** dst; };
+    size_t const nrd = static_cast<size_t>(b->n_reads);
+    Meta const ms[4] = {{meta->read_mapq, nrd, reinterpret_cast<const void**>(&d->read_mapq)},
+                        {meta->read_mflags, nrd, reinterpret_cast<const void**>(&d->read_mflags)},
+                        {meta->read_isize, 4 * nrd, reinterpret_cast<const void**>(&d->read_isize)},
+                        {meta->read_start, 4 * nrd, reinterpret_cast<const void**>(&d->read_start)}};
+    for (int i = 0; i < 4; ++i) {
+      MA_HIP(ctx, ctx->in_stage[12 + i].reserve(ms[i].bytes + 16));
+      if (ms[i].bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->in_stage[12 + i].p, ms[i].src, ms[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+      *ms[i].dst = ctx->in_stage[12 + i].p;
+    }
   }
   return MA_OK;
 }
@@ -215,7 +240,7 @@ void advance_fields(S* s, const std::vector<OutField>& per_unit, size_t first, s
 
 // One contiguous window range [w0, w1) of the batch on a child context.  All pointers are device pointers.
 int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, const DPacked* pk, int w0, int w1, u32 r0, u32 r1, ma_gate_out_t g,
-             ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, ma_fmt_out_t f, int lane_index) {
+             ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, ma_fmt_out_t f, ma_fmt_meta_out_t fm, int lane_index) {
   MA_HIP(ch, hipSetDevice(ch->device));
   MA_HIP(ch, hipStreamWaitEvent(ch->stream, start, 0));
   (void)lane_index;  // (starting the lanes a few ms apart was measured: every ms of stagger is lost, the lanes do overlap)
@@ -234,6 +259,13 @@ int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, const DPacked* pk
   d.read_sample = full.read_sample + r0;
   d.read_flags = full.read_flags + r0;
   d.read_hint = full.read_hint ? full.read_hint + r0 : nullptr;
+  if (full.read_mapq) {
+    d.read_mapq = full.read_mapq + r0; d.read_mflags = full.read_mflags + r0;
+    d.read_isize = full.read_isize + r0; d.read_start = full.read_start + r0;
+  } else {  // (all four null or all four set: ma_internal.h)
+    d.read_mapq = d.read_mflags = nullptr;
+    d.read_isize = d.read_start = nullptr;
+  }
   ma_params_t const& p = ch->prm;
   advance_fields(&g, gate_fields(p, 1), 0, 2, w0);
   advance_fields(&a, asm_fields(p, 1), 0, 99, w0);
@@ -243,11 +275,12 @@ int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, const DPacked* pk
   advance_fields(&q, gf, 2, 6, r0);   // alignment / assignment taps: per read
   advance_fields(&q, gf, 6, 8, w0);   // PL, GQ: per window
   advance_fields(&f, fmt_fields(p, 1), 0, 99, w0);  // (all null without the statistics)
+  advance_fields(&fm, fmeta_fields(p, 1), 0, 99, w0);
   if (pk) MA_TRY_RC(launch_unpack(ch, *pk, d.read_off, r0, static_cast<u64>(r1) - r0));  // a packed call: the lane's reads first
   MA_TRY_RC(launch_gate(ch, d, g.max_approx, g.max_exact));
   MA_TRY_RC(launch_assemble(ch, d, a, g.max_approx));
   MA_TRY_RC(launch_msa(ch, d, a, v));
-  MA_TRY_RC(launch_genotype(ch, d, a, v, q, &f));
+  MA_TRY_RC(launch_genotype(ch, d, a, v, q, &f, &fm));
   MA_HIP(ch, hipEventRecord(ch->lane_done, ch->stream));
   return MA_OK;
 }
@@ -310,7 +343,7 @@ struct DevLanePool {
 };
 
 int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk, const ma_gate_out_t& g, const ma_asm_out_t& a,
-                     const ma_var_out_t& v, const ma_geno_out_t& q, const ma_fmt_out_t& f) {
+                     const ma_var_out_t& v, const ma_geno_out_t& q, const ma_fmt_out_t& f, const ma_fmt_meta_out_t& fm) {
   while (static_cast<int>(ctx->lanes.size()) < lanes) {
     ma_ctx* ch = new (std::nothrow) ma_ctx();
     if (!ch) return MA_ERR_NOMEM;
@@ -341,7 +374,7 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk,
   }
   if (!ctx->dev_pool) ctx->dev_pool = new DevLanePool();
   static_cast<DevLanePool*>(ctx->dev_pool)->run(lanes, [&](int k) {
-    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, pk, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, k);
+    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, pk, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, fm, k);
   });
   for (int k = 0; k < lanes; ++k) {
     if (rc[k] != MA_OK) {
@@ -372,6 +405,7 @@ struct LaneOut {
   ma_var_out_t v{};
   ma_geno_out_t q{};
   ma_fmt_out_t f{};
+  ma_fmt_meta_out_t m{};
 };
 
 int ensure_pinned(ma_ctx* ch, int set, size_t bytes) {
@@ -398,7 +432,7 @@ int alloc_fields(ma_ctx* ch, S* dev, const std::vector<OutField>& f, size_t stag
   return MA_OK;
 }
 
-// The output arrays of the route, as tables: which struct (0 gate, 1 asm, 2 var, 3 geno, 4 fmt) and member, bytes per window.
+// The output arrays of the route, as tables: which struct (0 gate, 1 asm, 2 var, 3 geno, 4 fmt, 5 fmeta) and member, bytes per window.
 struct DenseDesc { int strct; size_t off; size_t win_bytes; };  // small per-window arrays: copied whole
 struct SegDesc { int strct; size_t off; size_t win_stride, unit; u32 kind; };  // packed: only what a window uses
 std::vector<DenseDesc> dense_table(const ma_params_t& p) {
@@ -431,11 +465,16 @@ std::vector<SegDesc> seg_table(const ma_params_t& p) {
           var(3, off_of(&ma_geno_out_t::var_pl), 4, S * G), var(3, off_of(&ma_geno_out_t::var_gq), 4, S),
           // entries 19 .. 22: the read-level FORMAT statistics (kSegFmt0: lane_compute's allocation goes by these numbers)
           var(4, off_of(&ma_fmt_out_t::ev_sums), 4, S * (MA_ + 1) * 3), var(4, off_of(&ma_fmt_out_t::fmt_npbq), 8, S * (MA_ + 1)),
-          var(4, off_of(&ma_fmt_out_t::fmt_cmlod), 8, S * MA_), var(4, off_of(&ma_fmt_out_t::fmt_stat), 8, S * 4)};
+          var(4, off_of(&ma_fmt_out_t::fmt_cmlod), 8, S * MA_), var(4, off_of(&ma_fmt_out_t::fmt_stat), 8, S * 4),
+          // entries 23 .. 26: the statistics over the read metadata (kSegMeta0)
+          var(5, off_of(&ma_fmt_meta_out_t::ev_meta), 8, S * (MA_ + 1) * 4), var(5, off_of(&ma_fmt_meta_out_t::ev_rpcd), 8, S * 4),
+          var(5, off_of(&ma_fmt_meta_out_t::fmt_rmq), 8, S * (MA_ + 1)), var(5, off_of(&ma_fmt_meta_out_t::fmt_mstat), 8, S * 5)};
 }
-constexpr int kSegFmt0 = 19;  // seg_table: first entry of the statistics
-struct OutPtrs {  // the five output structs of a call, by table index (the fifth, the statistics, may be null)
-  const void* s[5];
+constexpr int kSegFmt0 = 19;   // seg_table: first entry of the statistics
+constexpr int kSegMeta0 = 23;  // ... and of those over the read metadata
+constexpr u32 kSegMetaMask = 0xFu << kSegMeta0;
+struct OutPtrs {  // the six output structs of a call, by table index (the last two, the statistics, may be null)
+  const void* s[6];
   void* at(int strct, size_t off) const { return s[strct] ? ptr_at(s[strct], off) : nullptr; }
 };
 // which packed arrays the caller asked for (bit i = entry i of seg_table)
@@ -504,7 +543,7 @@ int run_copy_ops(ma_ctx* owner, hipStream_t stream, std::vector<CopyOp> const& o
 // the copies have run).  A packed batch (pk): the nibble arrays of the slice go into bufs[10] / [11] in place of the read
 // bases and -- 4-bit -- qualities; bufs[4] / [5] get their zero pads only, *dpk says how k_unpack_reads fills the rest.
 int stage_lane_inputs(ma_ctx* ch, int set, const ma_batch_t* b, int w0, int w1, std::vector<CopyOp>* ops, DBatch* d,
-                      const ma_packed_reads_t* pk = nullptr, DPacked* dpk = nullptr) {
+                      const ma_packed_reads_t* pk = nullptr, DPacked* dpk = nullptr, const ma_read_meta_t* meta = nullptr) {
   int const n = w1 - w0;
   u32 const r0 = b->read_win_off[w0], r1 = b->read_win_off[w1];
   size_t const nr = static_cast<size_t>(r1) - r0;
@@ -569,6 +608,24 @@ int stage_lane_inputs(ma_ctx* ch, int set, const ma_batch_t* b, int w0, int w1, 
   d->read_sample = reinterpret_cast<const u8*>(dp[7]);
   d->read_flags = reinterpret_cast<const u8*>(dp[8]);
   d->read_hint = b->read_hint ? reinterpret_cast<const i32*>(dp[9]) : nullptr;
+  if (meta) {  // the slice of the four metadata arrays, into bufs[12 .. 15]
+    struct Meta { const void* src; size_t bytes; };
+    Meta const ms[4] = {{meta->read_mapq + r0, nr}, {meta->read_mflags + r0, nr}, {meta->read_isize + r0, 4 * nr},
+                        {meta->read_start + r0, 4 * nr}};
+    char* mp[4];
+    for (int i = 0; i < 4; ++i) {
+      MA_HIP(ch, in.bufs[12 + i].reserve(ms[i].bytes + kPad + 16));
+      mp[i] = static_cast<char*>(in.bufs[12 + i].p);
+      ops->push_back(CopyOp{mp[i], ms[i].src, ms[i].bytes});
+    }
+    d->read_mapq = reinterpret_cast<const u8*>(mp[0]);
+    d->read_mflags = reinterpret_cast<const u8*>(mp[1]);
+    d->read_isize = reinterpret_cast<const i32*>(mp[2]);
+    d->read_start = reinterpret_cast<const i32*>(mp[3]);
+  } else {  // (all four null or all four set: ma_internal.h)
+    d->read_mapq = d->read_mflags = nullptr;
+    d->read_isize = d->read_start = nullptr;
+  }
   return MA_OK;
 }
 
@@ -617,6 +674,8 @@ struct HostJob {
   bool packed = false;                // a packed batch: `pk` is a copy of the caller's struct, staged_pk the lanes' views
   ma_packed_reads_t pk{};
   std::vector<DPacked> staged_pk;
+  bool has_meta = false;              // the batch came with read metadata: `meta` is a copy of the caller's struct
+  ma_read_meta_t meta{};
   const ma_geno_out_t* taps = nullptr;  // the caller's struct when it asked for the per-read taps (never on a job queued ahead)
   std::vector<LaneResult> res;
   std::mutex mu;
@@ -688,7 +747,8 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     if (job.packed) dpk = job.staged_pk[k];
   } else {
     std::vector<CopyOp> ops;
-    MA_TRY_RC(stage_lane_inputs(ch, set, b, w0, w1, &ops, &d, job.packed ? &job.pk : nullptr, &dpk));
+    MA_TRY_RC(stage_lane_inputs(ch, set, b, w0, w1, &ops, &d, job.packed ? &job.pk : nullptr, &dpk,
+                                job.has_meta ? &job.meta : nullptr));
     MA_TRY_RC(run_copy_ops(ch, ch->stream, ops, std::vector<size_t>(), [](size_t) {}));
   }
   // ---- device-side outputs of the lane (fixed strides, as the kernels write them) ----
@@ -713,6 +773,10 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     std::vector<bool> need_f(ff.size(), false);  // the statistics the caller asked for (none: nothing is allocated)
     for (size_t i = 0; i < ff.size(); ++i) need_f[i] = (job.mask >> (kSegFmt0 + i)) & 1u;
     MA_TRY_RC(alloc_fields(ch, &o.f, ff, 44, need_f));
+    std::vector<OutField> const mf = fmeta_fields(p, n);
+    std::vector<bool> need_m(mf.size(), false);
+    for (size_t i = 0; i < mf.size(); ++i) need_m[i] = (job.mask >> (kSegMeta0 + i)) & 1u;
+    MA_TRY_RC(alloc_fields(ch, &o.m, mf, 48, need_m));
   }
   if (job.packed) MA_TRY_RC(launch_unpack(ch, dpk, d.read_off, r0, nr));  // after the slice's copies, before the gate
   t_up = since();
@@ -722,10 +786,10 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   t_asm = since();
   MA_TRY_RC(launch_msa(ch, d, o.a, o.v));
   t_msa = since();
-  MA_TRY_RC(launch_genotype(ch, d, o.a, o.v, o.q, &o.f));
+  MA_TRY_RC(launch_genotype(ch, d, o.a, o.v, o.q, &o.f, &o.m));
   t_geno = since();
   // ---- results: the small dense arrays whole, the rest as packed records, all into the landing area ----
-  OutPtrs const dev{{&o.g, &o.a, &o.v, &o.q, &o.f}};
+  OutPtrs const dev{{&o.g, &o.a, &o.v, &o.q, &o.f, &o.m}};
   size_t const N = n, MH = p.max_haps, MV = p.max_vars, MCG = p.max_cigar;
   std::vector<DenseDesc> const dense = dense_table(p);
   PackArgs D{};
@@ -827,6 +891,8 @@ void lane_deliver(const ma_params_t& p, HostJob const& job, int k, OutPtrs const
     // the used ones
     if (segs[i].strct == 4)
       std::memset(hp + W0 * segs[i].win_stride, segs[i].off == off_of(&ma_fmt_out_t::fmt_stat) ? 0xFF : 0, N * segs[i].win_stride);
+    if (segs[i].strct == 5)
+      std::memset(hp + W0 * segs[i].win_stride, segs[i].off == off_of(&ma_fmt_meta_out_t::fmt_mstat) ? 0xFF : 0, N * segs[i].win_stride);
     H.seg[H.nseg++] = PackSeg{hp + W0 * segs[i].win_stride, static_cast<u32>(segs[i].win_stride), static_cast<u32>(segs[i].unit),
                               segs[i].kind};
   }
@@ -1004,7 +1070,8 @@ void forget_views(ma_ctx* ctx) {
 
 // queue the lanes' jobs of batch `b`, whose inputs are (being) staged in `set` when `ready`
 std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, int set,
-                                     std::shared_ptr<UploadTask> upload, u32 mask, const ma_geno_out_t* taps) {
+                                     std::shared_ptr<UploadTask> upload, u32 mask, const ma_geno_out_t* taps,
+                                     const ma_read_meta_t* meta) {
   HostAsync* ha = async_of(ctx);
   auto job = std::make_shared<HostJob>();
   job->batch = *b;
@@ -1025,6 +1092,10 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
     job->pk = *pk;
     if (upload) job->staged_pk = views_of(ctx).pk[set];
   }
+  if (meta) {
+    job->has_meta = true;
+    job->meta = *meta;
+  }
   job->taps = taps;
   job->res.resize(lanes);
   for (int k = 0; k < lanes; ++k) {
@@ -1038,11 +1109,12 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
   return job;
 }
 
-int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* g,
-                 const ma_asm_out_t* a, const ma_var_out_t* v, const ma_geno_out_t* q, const ma_fmt_out_t* f) {
+int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_read_meta_t* meta,
+                 const ma_gate_out_t* g, const ma_asm_out_t* a, const ma_var_out_t* v, const ma_geno_out_t* q,
+                 const ma_fmt_out_t* f, const ma_fmt_meta_out_t* fm) {
   MA_TRY_RC(ensure_workers(ctx, lanes));
   HostAsync* ha = async_of(ctx);
-  OutPtrs const user{{g, a, v, q, f}};
+  OutPtrs const user{{g, a, v, q, f, fm}};
   u32 const mask = seg_mask_of(ctx->prm, user);
   bool const taps = wants_taps(q);
   // did ma_prefetch_batch upload this batch?  (the oldest set that holds it); otherwise any set that holds nothing
@@ -1051,13 +1123,16 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
   for (int s = 0; s < 2; ++s) {
     if (ctx->pf_batch[s] != b || ctx->pf_sig[s][0] != b->n_windows || ctx->pf_sig[s][1] != b->n_reads || ctx->pf_sig[s][2] != lanes)
       continue;
-    if (ctx->pf_pk[s] != pk) {  // queued as ASCII and brought packed, or the other way round: dropped, computed below
+    if (ctx->pf_pk[s] != pk || (meta && ctx->pf_meta[s] != meta)) {  // queued as ASCII and brought packed, or the other way
+      // round, or the call wants the statistics over read metadata the upload did not bring: dropped, computed below.  (A call
+      // that does not want them -- meta is null here -- takes the staged batch whatever metadata came with it.)
       if (ha->jobs[s]) ha->jobs[s]->wait_all();
       ha->jobs[s].reset();
       if (ha->uploads[s]) ha->uploads[s]->wait();
       ha->uploads[s].reset();
       ctx->pf_batch[s] = nullptr;
       ctx->pf_pk[s] = nullptr;
+      ctx->pf_meta[s] = nullptr;
       continue;
     }
     if (set < 0 || ctx->pf_seq[s] < ctx->pf_seq[set]) {
@@ -1074,6 +1149,7 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
       ha->uploads[set].reset();
       ctx->pf_batch[set] = nullptr;
       ctx->pf_pk[set] = nullptr;
+      ctx->pf_meta[set] = nullptr;
     }
   }
   std::shared_ptr<HostJob> job = ha->jobs[set];
@@ -1083,7 +1159,7 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
     job.reset();
   }
   if (!prefetched) ha->uploads[set].reset();
-  if (!job) job = submit_host(ctx, lanes, b, pk, set, prefetched ? ha->uploads[set] : nullptr, mask, taps ? q : nullptr);
+  if (!job) job = submit_host(ctx, lanes, b, pk, set, prefetched ? ha->uploads[set] : nullptr, mask, taps ? q : nullptr, meta);
   ha->jobs[set] = job;
   ha->last_mask = mask;
   ha->have_mask = true;
@@ -1117,6 +1193,7 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
   ha->uploads[set].reset();
   ctx->pf_batch[set] = nullptr;  // consumed (or used as plain staging): free for the next prefetch
   ctx->pf_pk[set] = nullptr;
+  ctx->pf_meta[set] = nullptr;
   return rc;
 }
 
@@ -1179,6 +1256,7 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->ws_aln.release(); ctx->ws_misc.release(); ctx->ws_cx.release(); ctx->ws_gen.release(); ctx->ws_mm.release(); ctx->dev_stats.release();
   ctx->pack_aux.release();
   ctx->ws_unpack.release();
+  ctx->ws_sort.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
     pp = nullptr;
@@ -1376,12 +1454,26 @@ int ma_msa_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, c
   return MA_OK;
 }
 
-int ma_genotype_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
-                            const ma_geno_out_t* out, const ma_fmt_out_t* fmt) {
+// the read metadata a call needs: none without the statistics over it (meta is then not read); all four arrays with them
+static int check_meta(const ma_read_meta_t** meta, const ma_fmt_meta_out_t** fmeta) {
+  if (!*fmeta || !fmeta_wanted(**fmeta)) {
+    *meta = nullptr;
+    *fmeta = nullptr;
+    return MA_OK;
+  }
+  const ma_read_meta_t* m = *meta;
+  if (!m || !m->read_mapq || !m->read_mflags || !m->read_isize || !m->read_start) return MA_ERR_ARG;
+  return MA_OK;
+}
+
+int ma_genotype_meta_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_read_meta_t* meta, const ma_asm_out_t* asmb,
+                           const ma_var_out_t* vars, const ma_geno_out_t* out, const ma_fmt_out_t* fmt,
+                           const ma_fmt_meta_out_t* fmeta) {
   MA_BEGIN(ctx);
   if (!out || !asmb || !vars) return MA_ERR_ARG;
+  MA_TRY(check_meta(&meta, &fmeta));
   DBatch d;
-  MA_TRY(stage_batch(ctx, b, &d));
+  MA_TRY(stage_batch(ctx, b, &d, meta));
   OutMirror<ma_asm_out_t> a;
   MA_TRY(a.prepare(ctx, asmb, asm_fields(ctx->prm, d.n_windows), 2, true));
   OutMirror<ma_var_out_t> v;
@@ -1390,15 +1482,23 @@ int ma_genotype_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out
   MA_TRY(g.prepare(ctx, out, geno_fields(ctx->prm, d.n_windows, d.n_reads), 32, false));
   OutMirror<ma_fmt_out_t> f;  // (fmt null: all members null, the stage without the statistics)
   MA_TRY(f.prepare(ctx, fmt, fmt_fields(ctx->prm, d.n_windows), 44, false));
-  MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, g.dev, &f.dev));
+  OutMirror<ma_fmt_meta_out_t> fm;
+  MA_TRY(fm.prepare(ctx, fmeta, fmeta_fields(ctx->prm, d.n_windows), 48, false));
+  MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, g.dev, &f.dev, &fm.dev));
   MA_TRY(g.download(ctx));
   MA_TRY(f.download(ctx));
+  MA_TRY(fm.download(ctx));
   // win_status may gain MA_W_CIGAR_OVERFLOW / MA_W_READ_OVERFLOW
   if (ctx->memspace == MA_MEM_HOST) {
     MA_HIP(ctx, hipMemcpyAsync(asmb->win_status, a.dev.win_status, 4ull * d.n_windows, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));
   }
   return MA_OK;
+}
+
+int ma_genotype_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
+                            const ma_geno_out_t* out, const ma_fmt_out_t* fmt) {
+  return ma_genotype_meta_batch(ctx, b, nullptr, asmb, vars, out, fmt, nullptr);
 }
 
 int ma_genotype_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
@@ -1433,7 +1533,7 @@ static int check_packed(const ma_batch_t* b, const ma_packed_reads_t* pk) {
   return MA_OK;
 }
 
-static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* pk) {
+static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* pk, const ma_read_meta_t* meta = nullptr) {
   if (!ctx || !next) return MA_ERR_ARG;
   if (ctx->memspace != MA_MEM_HOST || next->n_windows <= 0 || getenv("MA_HOST_LEGACY")) return MA_OK;  // nothing to stage
   MA_HIP(ctx, hipSetDevice(ctx->device));
@@ -1453,7 +1553,7 @@ static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_r
       task->lane_end.push_back(task->ops.size());
       continue;
     }
-    int const rc = stage_lane_inputs(ctx->lanes[k], set, next, wb[k], wb[k + 1], &task->ops, &pv.d[set][k], pk, &pv.pk[set][k]);
+    int const rc = stage_lane_inputs(ctx->lanes[k], set, next, wb[k], wb[k + 1], &task->ops, &pv.d[set][k], pk, &pv.pk[set][k], meta);
     if (rc != MA_OK) {
       ma_set_err(ctx, "prefetch, lane " + std::to_string(k) + ": " + ma_get_err(ctx->lanes[k]));
       return rc;
@@ -1470,6 +1570,7 @@ static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_r
   ha->uploads[set] = task;
   ctx->pf_batch[set] = next;
   ctx->pf_pk[set] = pk;
+  ctx->pf_meta[set] = meta;
   ctx->pf_sig[set][0] = next->n_windows;
   ctx->pf_sig[set][1] = next->n_reads;
   ctx->pf_sig[set][2] = lanes;
@@ -1477,8 +1578,10 @@ static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_r
   // ... and its compute jobs behind whatever the lanes are doing: the call that brings the batch will find the records
   // waiting (or on their way).  Not in the statistics-gathering mode of the bench (its device counters are per call).
   ha->jobs[set].reset();
+  // (a batch without read metadata cannot compute the statistics over it: queued without them -- and computed again, from a
+  //  fresh upload, if the call then wants them)
   if (ha->have_mask && !ctx->collect)
-    ha->jobs[set] = submit_host(ctx, lanes, next, pk, set, task, ha->last_mask, nullptr);
+    ha->jobs[set] = submit_host(ctx, lanes, next, pk, set, task, meta ? ha->last_mask : ha->last_mask & ~kSegMetaMask, nullptr, meta);
   return MA_OK;
 }
 
@@ -1488,6 +1591,14 @@ int ma_prefetch_packed_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_pac
   if (!ctx) return MA_ERR_ARG;
   MA_TRY(check_packed(next, next_pk));
   return prefetch_any(ctx, next, next_pk);
+}
+
+int ma_prefetch_meta_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* next_pk, const ma_read_meta_t* next_meta) {
+  if (!ctx) return MA_ERR_ARG;
+  if (next_pk) MA_TRY(check_packed(next, next_pk));
+  if (next_meta && (!next_meta->read_mapq || !next_meta->read_mflags || !next_meta->read_isize || !next_meta->read_start))
+    return MA_ERR_ARG;
+  return prefetch_any(ctx, next, next_pk, next_meta);
 }
 
 int ma_process_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
@@ -1542,9 +1653,11 @@ static int stage_packed(ma_ctx* ctx, const ma_batch_t* b, const ma_packed_reads_
 }
 
 static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* gate,
-                       const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt) {
+                       const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt,
+                       const ma_read_meta_t* meta = nullptr, const ma_fmt_meta_out_t* fmeta = nullptr) {
   MA_BEGIN(ctx);
   if (!gate || !asmb || !vars || !geno) return MA_ERR_ARG;
+  MA_TRY(check_meta(&meta, &fmeta));
   if (!gate->max_approx || !gate->max_exact || !geno->allele_counts || !geno->var_qual) return MA_ERR_ARG;
   if (ctx->memspace == MA_MEM_HOST && !getenv("MA_HOST_LEGACY")) {
     // the host route: every lane uploads its own slice, computes, and brings back packed records (see process_host).
@@ -1554,7 +1667,7 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
     if (!asmb->win_status || !asmb->win_ncomp || !asmb->comp_hap0 || !asmb->comp_nhaps || !asmb->hap_len ||
         !asmb->hap_nruns || !vars->win_nvars)
       return MA_ERR_ARG;
-    return process_host(ctx, host_lanes(ctx, b->n_windows), b, pk, gate, asmb, vars, geno, fmt);
+    return process_host(ctx, host_lanes(ctx, b->n_windows), b, pk, meta, gate, asmb, vars, geno, fmt, fmeta);
   }
   DBatch d;
   DPacked dp{};
@@ -1562,10 +1675,10 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
     if (b->n_windows <= 0) return b->n_windows == 0 ? MA_OK : MA_ERR_ARG;
     ma_batch_t bb = *b;
     if (pk->qual_bits == 8) bb.read_quals = pk->quals;
-    MA_TRY(stage_batch(ctx, &bb, &d));
+    MA_TRY(stage_batch(ctx, &bb, &d, meta));
     MA_TRY(stage_packed(ctx, b, pk, &d, &dp));
   } else {
-    MA_TRY(stage_batch(ctx, b, &d));
+    MA_TRY(stage_batch(ctx, b, &d, meta));
   }
   OutMirror<ma_gate_out_t> g;
   MA_TRY(g.prepare(ctx, gate, gate_fields(ctx->prm, d.n_windows), 0, false));
@@ -1577,6 +1690,8 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
   MA_TRY(q.prepare(ctx, geno, geno_fields(ctx->prm, d.n_windows, d.n_reads), 32, false));
   OutMirror<ma_fmt_out_t> f;  // (fmt null: all members null)
   MA_TRY(f.prepare(ctx, fmt, fmt_fields(ctx->prm, d.n_windows), 44, false));
+  OutMirror<ma_fmt_meta_out_t> fm;
+  MA_TRY(fm.prepare(ctx, fmeta, fmeta_fields(ctx->prm, d.n_windows), 48, false));
   // Automatic: three lanes for big batches -- the process has four hardware queues by default (ROCm's GPU_MAX_HW_QUEUES) and a
   // fourth lane would share one with the caller's stream (measured: -18 %); a host that raises GPU_MAX_HW_QUEUES to >= 6
   // before HIP starts gets four (+2 %).
@@ -1593,17 +1708,26 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
     MA_TRY(launch_gate(ctx, d, g.dev.max_approx, g.dev.max_exact));
     MA_TRY(launch_assemble(ctx, d, a.dev, g.dev.max_approx));
     MA_TRY(launch_msa(ctx, d, a.dev, v.dev));
-    MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, q.dev, &f.dev));
+    MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, q.dev, &f.dev, &fm.dev));
   } else {
-    MA_TRY(process_in_lanes(ctx, lanes, d, pk ? &dp : nullptr, g.dev, a.dev, v.dev, q.dev, f.dev));
+    MA_TRY(process_in_lanes(ctx, lanes, d, pk ? &dp : nullptr, g.dev, a.dev, v.dev, q.dev, f.dev, fm.dev));
   }
   MA_TRY(g.download(ctx));
   MA_TRY(a.download(ctx));
   MA_TRY(v.download(ctx));
   MA_TRY(q.download(ctx));
   MA_TRY(f.download(ctx));
+  MA_TRY(fm.download(ctx));
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
   return MA_OK;
+}
+
+int ma_process_meta_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_read_meta_t* meta,
+                          const ma_gate_out_t* gate, const ma_asm_out_t* asmb, const ma_var_out_t* vars,
+                          const ma_geno_out_t* geno, const ma_fmt_out_t* fmt, const ma_fmt_meta_out_t* fmeta) {
+  if (!ctx) return MA_ERR_ARG;
+  if (pk) MA_TRY(check_packed(b, pk));
+  return process_any(ctx, b, pk, gate, asmb, vars, geno, fmt, meta, fmeta);
 }
 
 int ma_process_stats_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,

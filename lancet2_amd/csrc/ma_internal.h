@@ -52,7 +52,8 @@ struct DevBuf {
 // One staged copy of a lane's slice of a host batch (MA_MEM_HOST route of ma_process_batch): two per lane, so that
 // ma_prefetch_batch can upload the next batch while this one computes.
 struct InputSet {
-  DevBuf bufs[12];  // [0..9] the batch arrays as the stages read them; [10], [11] the nibble arrays of a packed call
+  DevBuf bufs[16];  // [0..9] the batch arrays as the stages read them; [10], [11] the nibble arrays of a packed call;
+                    // [12..15] the read metadata of a call with ma_read_meta_t
   std::vector<uint32_t> h_rwo;  // the lane's rebased read_win_off while its upload is in flight
 };
 
@@ -72,10 +73,11 @@ struct ma_ctx {
   std::string err;     // last error: written through ma_set_err (worker threads of the host route write it too)
   std::mutex err_mu;
   // staging for MA_MEM_HOST
-  ma::DevBuf in_stage[12];  // ([10], [11]: the nibble arrays of a packed call)
+  ma::DevBuf in_stage[16];  // ([10], [11]: the nibble arrays of a packed call; [12..15]: the read metadata)
   ma::DevBuf ws_unpack;     // MA_MEM_DEVICE packed call: the expanded read bases (and 4-bit qualities)
   std::vector<ma::DevBuf> out_stage;
   // per-stage workspaces (grow-only, reused across calls)
+  ma::DevBuf ws_sort;  // k_evid_stats: sort slices of the cells that do not fit its LDS (evidence.hip)
   ma::DevBuf ws_build, ws_nodes, ws_clean, ws_aln, ws_misc, ws_gen, ws_mm;  // (ws_build: the assembly stage's arena, then the POA stage's)
   // speculative tail of the k ladder (assemble.hip: speculate_tail): the derived batch, its outputs and the bookkeeping of the
   // nested pass; spec_k = the rung every window of the nested pass is built at (null outside of it)
@@ -121,6 +123,7 @@ struct ma_ctx {
   const ma_batch_t* pf_batch[2] = {nullptr, nullptr};
   int64_t pf_sig[2][3] = {{0, 0, 0}, {0, 0, 0}};  // n_windows, n_reads, lanes of the prefetched batch
   const ma_packed_reads_t* pf_pk[2] = {nullptr, nullptr};  // ... and the packed-reads struct it came with (null: ASCII)
+  const ma_read_meta_t* pf_meta[2] = {nullptr, nullptr};   // ... and the read metadata (null: none)
   unsigned long long pf_seq[2] = {0, 0}, pf_counter = 0;
   hipStream_t copy_stream = nullptr;
 
@@ -195,6 +198,11 @@ struct DBatch {
   const u8* read_sample;
   const u8* read_flags;
   const i32* read_hint;  // may be null
+  // the read metadata of ma_read_meta_t: all four null, or all four set
+  const u8* read_mapq;
+  const u8* read_mflags;
+  const i32* read_isize;
+  const i32* read_start;
 };
 
 // A packed call's reads (ma_packed_reads_t) on the device, for k_unpack_reads (unpack.hip).  bases4 / quals4 are addressed
@@ -216,8 +224,9 @@ int launch_gate(ma_ctx* ctx, const DBatch& b, u32* max_approx, u32* max_exact);
 int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& o, const u32* gate_approx);
 int launch_msa(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o);
 // fmt: the read-level FORMAT statistics (evidence.hip); null, or all members null, is the stage without them
+// fmeta: the statistics over the read metadata of b.read_mapq ... b.read_start, likewise
 int launch_genotype(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& v,
-                    const ma_geno_out_t& o, const ma_fmt_out_t* fmt = nullptr);
+                    const ma_geno_out_t& o, const ma_fmt_out_t* fmt = nullptr, const ma_fmt_meta_out_t* fmeta = nullptr);
 int launch_annotate(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& v, double gc_frac,
                     const ma_cx_out_t& o);
 

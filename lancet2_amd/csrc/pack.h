@@ -29,7 +29,7 @@ struct PackArgs {
   const u32* alt_len;
   u32 MC, MH, MV, MA, MP;
   u32 nseg;
-  PackSeg seg[24];
+  PackSeg seg[28];  // (api.hip: seg_table has 27 entries)
 };
 
 // whole-array copies of k_pack_dense (sizes in bytes, multiples of 4)

@@ -39,6 +39,10 @@ def load_library(path=None):
     if hasattr(lib, "ma_process_packed_batch"):  # (absent from a build of before the packed calls given as `path` for an A/B)
         lib.ma_process_packed_batch.argtypes = [C.c_void_p] * 8
         lib.ma_prefetch_packed_batch.argtypes = [C.c_void_p] * 3
+    if hasattr(lib, "ma_process_meta_batch"):  # (likewise: a build of before the read-metadata calls)
+        lib.ma_genotype_meta_batch.argtypes = [C.c_void_p] * 8
+        lib.ma_process_meta_batch.argtypes = [C.c_void_p] * 10
+        lib.ma_prefetch_meta_batch.argtypes = [C.c_void_p] * 4
     lib.ma_annotate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.ma_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     lib.ma_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
@@ -155,6 +159,42 @@ class Engine:
                     "ma_genotype_stats_batch")
         return out, fmt
 
+    def _fmt_pair(self, n, fields, meta_fields):
+        fmt = self._alloc({k: s for k, s in capi.fmt_out_spec(self.p, n).items() if fields is None or k in fields})
+        fmeta = self._alloc({k: s for k, s in capi.fmt_meta_out_spec(self.p, n).items()
+                             if meta_fields is None or k in meta_fields})
+        return fmt, fmeta
+
+    def genotype_meta(self, arrs, meta, n, nr, asm, var, debug=False, fields=None, meta_fields=None):
+        """ma_genotype_meta_batch: genotype_stats() + the six statistics over the read metadata (`meta`: dict of the four
+        capi.META_DTYPES arrays; `meta_fields`: a subset of capi.fmt_meta_out_spec, default all).  Returns (geno, fmt, fmeta)."""
+        out = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))
+        fmt, fmeta = self._fmt_pair(n, fields, meta_fields)
+        b = capi.make_batch_struct(arrs, n, nr)
+        m = capi.fill_struct(capi.ReadMeta, meta)
+        self._check(self.lib.ma_genotype_meta_batch(self.h, C.byref(b), C.byref(m), C.byref(capi.fill_struct(capi.AsmOut, asm)),
+                                                    C.byref(capi.fill_struct(capi.VarOut, var)),
+                                                    C.byref(capi.fill_struct(capi.GenoOut, out)),
+                                                    C.byref(capi.fill_struct(capi.FmtOut, fmt)),
+                                                    C.byref(capi.fill_struct(capi.FmtMetaOut, fmeta))), "ma_genotype_meta_batch")
+        return out, fmt, fmeta
+
+    def process_meta(self, arrs, meta, n, nr, packed=None, debug=False, fields=None, meta_fields=None):
+        """ma_process_meta_batch: process_stats() -- process_packed() with `packed` (capi.pack_reads) -- + the statistics over
+        the read metadata.  Returns (gate, asm, var, geno, fmt, fmeta)."""
+        g = self._alloc(capi.gate_out_spec(n))
+        a = self._alloc(capi.asm_out_spec(self.p, n))
+        v = self._alloc(capi.var_out_spec(self.p, n))
+        q = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))
+        f, fm = self._fmt_pair(n, fields, meta_fields)
+        b = capi.make_batch_struct(capi.packed_batch_arrays(arrs) if packed is not None else arrs, n, nr)
+        pk = capi.make_packed_struct(packed) if packed is not None else None
+        m = capi.fill_struct(capi.ReadMeta, meta)
+        self.process_meta_device(b, pk, m, capi.fill_struct(capi.GateOut, g), capi.fill_struct(capi.AsmOut, a),
+                                 capi.fill_struct(capi.VarOut, v), capi.fill_struct(capi.GenoOut, q),
+                                 capi.fill_struct(capi.FmtOut, f), capi.fill_struct(capi.FmtMetaOut, fm))
+        return g, a, v, q, f, fm
+
     def annotate(self, arrs, n, nr, asm, var, gc_frac=0.41):
         """VariantAnnotator (core/variant_annotator.cpp:43-101): SEQ_CX + GRAPH_CX of every variant."""
         out = self._alloc(capi.cx_out_spec(self.p, n))
@@ -233,6 +273,26 @@ class Engine:
         """MA_MEM_HOST: ma_prefetch_packed_batch -- prefetch() for the batch the next process_packed_device() call brings"""
         self._check(self.lib.ma_prefetch_packed_batch(self.h, C.byref(batch_struct), C.byref(packed_struct)),
                     "ma_prefetch_packed_batch")
+
+    def genotype_meta_device(self, batch_struct, meta_struct, asm, var, geno, fmt=None, fmeta=None):
+        """ma_genotype_meta_batch on caller-made structs (either memory space); None: a null pointer"""
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        self._check(self.lib.ma_genotype_meta_batch(self.h, C.byref(batch_struct), ref(meta_struct), C.byref(asm), C.byref(var),
+                                                    C.byref(geno), ref(fmt), ref(fmeta)), "ma_genotype_meta_batch")
+
+    def process_meta_device(self, batch_struct, packed_struct, meta_struct, gate, asm, var, geno, fmt=None, fmeta=None):
+        """ma_process_meta_batch on caller-made structs (either memory space); packed_struct=None: an ASCII batch"""
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        self._check(self.lib.ma_process_meta_batch(self.h, C.byref(batch_struct), ref(packed_struct), ref(meta_struct),
+                                                   C.byref(gate), C.byref(asm), C.byref(var), C.byref(geno), ref(fmt), ref(fmeta)),
+                    "ma_process_meta_batch")
+
+    def prefetch_meta(self, batch_struct, packed_struct, meta_struct):
+        """MA_MEM_HOST: ma_prefetch_meta_batch -- prefetch() for the batch the next process_meta_device() call brings; the
+        arguments in the C call's order (packed_struct=None: an ASCII batch)"""
+        self._check(self.lib.ma_prefetch_meta_batch(self.h, C.byref(batch_struct),
+                                                    C.byref(packed_struct) if packed_struct is not None else None,
+                                                    C.byref(meta_struct)), "ma_prefetch_meta_batch")
 
     def annotate_device(self, batch_struct, asm, var, cx, gc_frac=0.41):
         self._check(self.lib.ma_annotate_batch(self.h, C.byref(batch_struct), C.byref(asm), C.byref(var),

@@ -113,6 +113,19 @@ struct SamRecord {
     return s > 0 ? s : 1;
   }
   uint32_t LeadingSoftClip() const { return !cigar.empty() && cigar.front().op == 'S' ? cigar.front().len : 0u; }
+  // cbdg::Read::IsSoftClipped (cbdg/read.h:39-50): the bases of ALL S operations of the record's CIGAR, at least 6 % of the read
+  bool IsSoftClipped() const {
+    uint32_t clip = 0;
+    for (auto const& c : cigar)
+      if (c.op == 'S') clip += c.len;
+    size_t const len = SeqLen();
+    double const frac = len > 0 ? static_cast<double>(clip) / static_cast<double>(len) : 0.0;
+    return frac >= 0.06;
+  }
+  // the four facts of ma_read_meta_t (include/microasm.h): MAPQ is `mapq`; the MA_RM_* bits, the insert size, the start
+  uint8_t MetaFlags() const { return static_cast<uint8_t>((IsSoftClipped() ? MA_RM_SOFTCLIP : 0) | (IsMappedProperPair() ? MA_RM_PROPER : 0)); }
+  int32_t InsertSize32() const { return static_cast<int32_t>(std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, tlen))); }
+  int32_t Start32() const { return static_cast<int32_t>(std::max<int64_t>(0, std::min<int64_t>(INT32_MAX, pos0))); }
 };
 
 inline std::vector<CigarUnit> ParseCigar(std::string_view s) {
@@ -757,10 +770,13 @@ struct Read {  // cbdg/read.h:22-60
   size_t sample_index = 0;
   uint32_t leading_clip = 0;
   bool passes = true;
+  uint8_t mflags = 0;   // MA_RM_* (SamRecord::MetaFlags)
+  int32_t isize = 0;    // InsertSize(): tlen
   Read() = default;
   Read(SamRecord const& a, std::string sname, Tag t, size_t sidx)
       : qname(a.qname), seq(a.seq), sample_name(std::move(sname)), qual(a.qual), start0(a.pos0), chrom(a.chrom),
-        flag(a.flag), mapq(a.mapq), tag(t), sample_index(sidx), leading_clip(a.LeadingSoftClip()), passes(a.mapq >= 20) {}
+        flag(a.flag), mapq(a.mapq), tag(t), sample_index(sidx), leading_clip(a.LeadingSoftClip()), passes(a.mapq >= 20),
+        mflags(a.MetaFlags()), isize(a.InsertSize32()) {}
 };
 
 // read_collector.cpp:42-53: filter-pass status > sample tag > sample name > qname > chrom > position
@@ -1001,6 +1017,10 @@ struct FlatBatch {
   std::vector<uint32_t> ref_off{0}, read_win_off{0}, read_qname_id;
   std::vector<uint64_t> read_off{0};
   std::vector<int32_t> read_hint;
+  // the read metadata of ma_read_meta_t, per read like read_hint: MAPQ, MA_RM_* bits, insert size (tlen), start (pos0)
+  std::vector<uint8_t> read_mapq, read_mflags;
+  std::vector<int32_t> read_isize, read_start;
+  ma_read_meta_t meta{};  // (Seal)
   std::vector<Window> windows;
   std::vector<std::vector<double>> sample_cov;  // [window][sample] sampled bases / window length
   ma_batch_t view{};
@@ -1028,6 +1048,10 @@ struct FlatBatch {
       // where base 0 of the read is expected on the window (include/microasm.h: read_hint)
       int64_t const hint = r.chrom == w.chrom ? r.start0 - static_cast<int64_t>(w.start1 - 1) - static_cast<int64_t>(r.leading_clip) : INT64_MIN;
       read_hint.push_back(hint > INT32_MIN && hint < INT32_MAX ? static_cast<int32_t>(hint) : MA_NO_HINT);
+      read_mapq.push_back(r.mapq);
+      read_mflags.push_back(r.mflags);
+      read_isize.push_back(r.isize);
+      read_start.push_back(static_cast<int32_t>(std::max<int64_t>(0, std::min<int64_t>(INT32_MAX, r.start0))));
     }
     read_win_off.push_back(static_cast<uint32_t>(read_qname_id.size()));
   }
@@ -1046,6 +1070,10 @@ struct FlatBatch {
     read_flags.insert(read_flags.end(), o.read_flags.begin(), o.read_flags.end());
     read_qname_id.insert(read_qname_id.end(), o.read_qname_id.begin(), o.read_qname_id.end());
     read_hint.insert(read_hint.end(), o.read_hint.begin(), o.read_hint.end());
+    read_mapq.insert(read_mapq.end(), o.read_mapq.begin(), o.read_mapq.end());
+    read_mflags.insert(read_mflags.end(), o.read_mflags.begin(), o.read_mflags.end());
+    read_isize.insert(read_isize.end(), o.read_isize.begin(), o.read_isize.end());
+    read_start.insert(read_start.end(), o.read_start.begin(), o.read_start.end());
     for (size_t i = 1; i < o.ref_off.size(); ++i) ref_off.push_back(rb + o.ref_off[i]);
     for (size_t i = 1; i < o.read_off.size(); ++i) read_off.push_back(qb + o.read_off[i]);
     for (size_t i = 1; i < o.read_win_off.size(); ++i) read_win_off.push_back(nr + o.read_win_off[i]);
@@ -1079,6 +1107,8 @@ struct FlatBatch {
     read_flags.resize(placed_reads_);
     read_qname_id.resize(placed_reads_);
     read_hint.resize(placed_reads_);
+    read_mapq.resize(placed_reads_); read_mflags.resize(placed_reads_);
+    read_isize.resize(placed_reads_); read_start.resize(placed_reads_);
     read_off.resize(placed_reads_ + 1);
     read_off[0] = 0;
   }
@@ -1098,6 +1128,10 @@ struct FlatBatch {
     std::memcpy(read_flags.data() + pl.read0, o.read_flags.data(), nr);
     std::memcpy(read_qname_id.data() + pl.read0, o.read_qname_id.data(), nr * sizeof(uint32_t));
     std::memcpy(read_hint.data() + pl.read0, o.read_hint.data(), nr * sizeof(int32_t));
+    std::memcpy(read_mapq.data() + pl.read0, o.read_mapq.data(), nr);
+    std::memcpy(read_mflags.data() + pl.read0, o.read_mflags.data(), nr);
+    std::memcpy(read_isize.data() + pl.read0, o.read_isize.data(), nr * sizeof(int32_t));
+    std::memcpy(read_start.data() + pl.read0, o.read_start.data(), nr * sizeof(int32_t));
     for (size_t i = 1; i <= nr; ++i) read_off[pl.read0 + i] = pl.base0 + o.read_off[i];
   }
   size_t placed_ref_ = 0, placed_reads_ = 0;
@@ -1107,6 +1141,8 @@ struct FlatBatch {
     ref_bases.clear(); read_bases.clear(); read_quals.clear(); read_sample.clear(); read_flags.clear();
     ref_off.assign(1, 0); read_win_off.assign(1, 0); read_off.assign(1, 0);
     read_qname_id.clear(); read_hint.clear(); windows.clear(); sample_cov.clear();
+    read_mapq.clear(); read_mflags.clear(); read_isize.clear(); read_start.clear();
+    meta = ma_read_meta_t{};
     placed_ref_ = placed_reads_ = 0;
     placed_bases_ = 0;
     seq4.clear(); seq4_off.assign(1, 0); bases4.clear(); quals_packed.clear();
@@ -1118,6 +1154,7 @@ struct FlatBatch {
     windows.reserve(n_win); sample_cov.reserve(n_win); ref_off.reserve(n_win + 1); read_win_off.reserve(n_win + 1);
     ref_bases.reserve(n_ref + 64); read_bases.reserve(n_bases + 64); read_quals.reserve(n_bases + 64);
     read_sample.reserve(n_reads); read_flags.reserve(n_reads); read_qname_id.reserve(n_reads); read_hint.reserve(n_reads); read_off.reserve(n_reads + 1);
+    read_mapq.reserve(n_reads); read_mflags.reserve(n_reads); read_isize.reserve(n_reads); read_start.reserve(n_reads);
   }
   void Seal() {
     size_t const rb = ref_bases.size(), qb = read_quals.size();
@@ -1136,6 +1173,8 @@ struct FlatBatch {
     view.read_sample = read_sample.data();
     view.read_flags = read_flags.data();
     view.read_hint = read_hint.data();
+    meta.read_mapq = read_mapq.data(); meta.read_mflags = read_mflags.data();
+    meta.read_isize = read_isize.data(); meta.read_start = read_start.data();
   }
   // --packed-reads (include/microasm.h: ma_packed_reads_t), after Seal(): the batch's quality dictionary -- 4-bit codes into
   // the distinct Phred values in ascending order when there are at most 16 of them, the Phred bytes as they are (qual_bits =
@@ -1276,6 +1315,7 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
   fb.read_sample.resize(r0 + nr);
   fb.read_flags.resize(r0 + nr);
   fb.read_hint.resize(r0 + nr);
+  fb.read_mapq.resize(r0 + nr); fb.read_mflags.resize(r0 + nr); fb.read_isize.resize(r0 + nr); fb.read_start.resize(r0 + nr);
   // names -> ids in order of first appearance: open addressing on the name hash, the name itself compared on a hit
   size_t cap = 16;
   while (cap < 2 * nr + 2) cap <<= 1;
@@ -1326,6 +1366,10 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
     fb.read_flags[r0 + i] = static_cast<uint8_t>((a.mapq >= 20 ? MA_RF_PASS : 0) | (sm.tag == Tag::CASE ? MA_RF_CASE : 0) | ((a.flag & 0x10) ? MA_RF_REV : 0));
     int64_t const hint = a.chrom == w.chrom ? a.pos0 - static_cast<int64_t>(w.start1 - 1) - static_cast<int64_t>(a.LeadingSoftClip()) : INT64_MIN;
     fb.read_hint[r0 + i] = hint > INT32_MIN && hint < INT32_MAX ? static_cast<int32_t>(hint) : MA_NO_HINT;
+    fb.read_mapq[r0 + i] = a.mapq;
+    fb.read_mflags[r0 + i] = a.MetaFlags();
+    fb.read_isize[r0 + i] = a.InsertSize32();
+    fb.read_start[r0 + i] = a.Start32();
   }
   fb.read_win_off.push_back(static_cast<uint32_t>(fb.read_qname_id.size()));
   return true;
@@ -1349,6 +1393,9 @@ struct VariantRecord {
   // the read-level FORMAT statistics of ma_process_stats_batch (empty: not computed; NaN: missing, "." in the VCF)
   std::vector<std::vector<double>> npbq, cmlod;     // [sample][allele], [sample][ALT]
   std::vector<std::array<double, 4>> fmt_stat;      // [sample] BQCD, ASMD, AHDD, HSE
+  // ... and of ma_process_meta_batch (empty: not computed -- the six are then written as missing)
+  std::vector<std::vector<double>> rmq;             // [sample][allele]
+  std::vector<std::array<double, 5>> fmt_mstat;     // [sample] SCA, FLD, RPCD, MQCD, FSSE
   double pdcv = std::numeric_limits<double>::quiet_NaN();  // MaxAltPathCv of the variant's component (NaN: none)
   uint64_t TotalCoverage() const {
     uint64_t t = 0;
@@ -1428,10 +1475,11 @@ class VariantStore {
 // ---- VCF text (caller/variant_call.cpp:100-520, caller/sample_format_data.cpp:32-98, cli/vcf_header_builder.cpp:28-63) -------
 // The record layout, INFO field and the FORMAT key are the reference's.  Of the 24 FORMAT values the engine's outputs give 18:
 // GT, AD, ADF, ADR, DP, SB, SDFC, PRAD, PANG, PL and GQ from the allele depths, NPBQ, BQCD, ASMD, CMLOD, AHDD and HSE from
-// ma_process_stats_batch (RecordsOfBatch's `fmt`) and PDCV from the assembly's comp_cxf.  RMQ, MQCD, SCA, FLD and FSSE need
-// MAPQ, insert size, alignment start, clip and pair flags the batch does not carry, RPCD a per-call sort of f64 values: those
-// six are written as missing (".").  Values pass through f32 where the reference stores f32 (sample_format_data.cpp:32-98,
-// variant_call.cpp:368-373).
+// ma_process_stats_batch (RecordsOfBatch's `fmt`) and PDCV from the assembly's comp_cxf.  The other six -- RMQ, SCA, FLD,
+// RPCD, MQCD, FSSE -- come from ma_process_meta_batch over FlatBatch's read metadata (RecordsOfBatch's `fmeta`); a record
+// built without them writes the six as missing (".").  Values pass through f32 where the reference stores f32, and are
+// printed with its formats: RMQ %.1F per allele, SCA %.4f, FLD %.1f, RPCD / MQCD / FSSE %.4f (sample_format_data.cpp:32-98,
+// variant_call.cpp:171-204, :366-379).
 inline constexpr const char* kVcfFormatKey =
     "GT:AD:ADF:ADR:DP:RMQ:NPBQ:SB:SCA:FLD:RPCD:BQCD:MQCD:ASMD:SDFC:PRAD:PANG:CMLOD:FSSE:AHDD:HSE:PDCV:PL:GQ";
 inline double PolarRadius(double ref_depth, double alt_depth) {  // base/polar_coords.h:149-151
@@ -1586,10 +1634,13 @@ inline std::string AsVcfRecord(VariantRecord const& r, Reference const& ref, std
     };
     double const kNan = std::numeric_limits<double>::quiet_NaN();
     std::array<double, 4> const st = s < r.fmt_stat.size() ? r.fmt_stat[s] : std::array<double, 4>{kNan, kNan, kNan, kNan};
+    std::array<double, 5> const mt = s < r.fmt_mstat.size() ? r.fmt_mstat[s] : std::array<double, 5>{kNan, kNan, kNan, kNan, kNan};
     line += "\t" + gt + ":" + join(r.ad[s]) + ":" + (s < r.adf.size() ? join(r.adf[s]) : ".") + ":" +
-            (s < r.adr.size() ? join(r.adr[s]) : ".") + ":" + std::to_string(dp) + ":.:" + list(r.npbq, "%.1F", true) + ":" + sb +
-            ":.:.:.:" + num(st[0], "%.4f", true) + ":.:" + num(st[1], "%.3f", true) + ":" + sdfc + ":" + polar + ":" +
-            list(r.cmlod, "%.4F", false) + ":.:" + num(st[2], "%.3f", true) + ":" + num(st[3], "%.4f", true) + ":" +
+            (s < r.adr.size() ? join(r.adr[s]) : ".") + ":" + std::to_string(dp) + ":" + list(r.rmq, "%.1F", true) + ":" +
+            list(r.npbq, "%.1F", true) + ":" + sb + ":" + num(mt[0], "%.4f", true) + ":" + num(mt[1], "%.1f", true) + ":" +
+            num(mt[2], "%.4f", true) + ":" + num(st[0], "%.4f", true) + ":" + num(mt[3], "%.4f", true) + ":" +
+            num(st[1], "%.3f", true) + ":" + sdfc + ":" + polar + ":" +
+            list(r.cmlod, "%.4F", false) + ":" + num(mt[4], "%.4f", true) + ":" + num(st[2], "%.3f", true) + ":" + num(st[3], "%.4f", true) + ":" +
             num(r.pdcv, "%.4f", true) + ":" + pl + ":" + (s < r.gq.size() ? std::to_string(r.gq[s]) : ".");
   }
   return line;
@@ -1602,7 +1653,8 @@ inline std::string AsVcfRecord(VariantRecord const& r, Reference const& ref, std
 // returns every record (tests; callers that want the raw per-window table).
 inline std::vector<VariantRecord> RecordsOfBatch(const ma_params_t& p, FlatBatch const& fb, const ma_var_out_t& v, const ma_geno_out_t& q,
                                                  const ma_cx_out_t* cx = nullptr, bool supported_only = true,
-                                                 const ma_fmt_out_t* fmt = nullptr, const ma_asm_out_t* asmb = nullptr) {
+                                                 const ma_fmt_out_t* fmt = nullptr, const ma_asm_out_t* asmb = nullptr,
+                                                 const ma_fmt_meta_out_t* fmeta = nullptr) {
   std::vector<VariantRecord> out;
   int const MV = p.max_vars, MA = p.max_alts, S = p.num_samples, NA = MA + 1;
   for (size_t w = 0; w < fb.windows.size(); ++w) {
@@ -1638,6 +1690,14 @@ inline std::vector<VariantRecord> RecordsOfBatch(const ma_params_t& p, FlatBatch
           if (fmt->fmt_npbq) r.npbq.emplace_back(fmt->fmt_npbq + cell * NA, fmt->fmt_npbq + cell * NA + K);
           if (fmt->fmt_cmlod) r.cmlod.emplace_back(fmt->fmt_cmlod + cell * MA, fmt->fmt_cmlod + cell * MA + (K - 1));
           if (fmt->fmt_stat) r.fmt_stat.push_back({fmt->fmt_stat[cell * 4], fmt->fmt_stat[cell * 4 + 1], fmt->fmt_stat[cell * 4 + 2], fmt->fmt_stat[cell * 4 + 3]});
+        }
+        if (fmeta) {  // ... and the six over the read metadata
+          size_t const cell = vi * S + s;
+          if (fmeta->fmt_rmq) r.rmq.emplace_back(fmeta->fmt_rmq + cell * NA, fmeta->fmt_rmq + cell * NA + K);
+          if (fmeta->fmt_mstat) {
+            const double* m = fmeta->fmt_mstat + cell * 5;
+            r.fmt_mstat.push_back({m[0], m[1], m[2], m[3], m[4]});
+          }
         }
       }
       if (asmb && asmb->comp_cxf) {  // PDCV: MaxAltPathCv of the variant's component, -1 = no ALT path
