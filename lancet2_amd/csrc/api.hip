@@ -371,6 +371,7 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk,
     ch->collect = ctx->collect;
     if (!ch->accumulate) ch->timers_used = 0;
     ch->hbm_share = ctx->hbm_share / lanes;
+    ch->co_lanes = lanes;
   }
   if (!ctx->dev_pool) ctx->dev_pool = new DevLanePool();
   static_cast<DevLanePool*>(ctx->dev_pool)->run(lanes, [&](int k) {
@@ -722,6 +723,7 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   ch->accumulate = job.accumulate;
   ch->collect = job.collect;
   ch->hbm_share = job.hbm_share;
+  ch->co_lanes = static_cast<int>(job.wb.size()) - 1;
   ch->timers_used = 0;
   for (auto& s : ch->stats) s = 0;
   ma_params_t const& p = ch->prm;

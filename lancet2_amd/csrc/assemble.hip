@@ -14,7 +14,7 @@ namespace ma {
 int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev, int tc_log2_alloc);
 int run_count_inst(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, int win0, int nwin, u32* maxima_dev);
 int run_select_active(ma_ctx* ctx, const GraphWs& ws, int win0, int nwin, const u32* gate_approx, u32* win_k,
-                      u32* active, u32* n_active_dev);
+                      u32* active, u32* n_active_dev, u32* pass_ctr);
 int run_clean_pass(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm_out_t& out);
 
 namespace {
@@ -87,7 +87,8 @@ __global__ __launch_bounds__(256) void k_workload_stats(GraphWs ws, unsigned lon
 }
 
 // Capacity retry: windows whose graph did not fit the node array / search arena are put back to "pending" so that the
-// next pass, with larger capacities, assembles them from scratch; counts them.
+// next pass, with larger capacities, assembles them from scratch; counts them (count[0]), and among them the windows a
+// common-route-only pass handed over because they need a general kernel (count[1]: kDeferBit, build.hip run_build_pass).
 __global__ void k_reset_overflowed(ma_asm_out_t o, u32* win_flags, int n, u32* count) {
   int const i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -95,6 +96,7 @@ __global__ void k_reset_overflowed(ma_asm_out_t o, u32* win_flags, int n, u32* c
   o.win_status[i] = MA_W_NO_HAPLOTYPE;
   o.win_k[i] = 0;
   o.win_ncomp[i] = 0;
+  if (win_flags[i] & kDeferBit) atomicAdd(count + 1, 1u);
   win_flags[i] = 0;
   atomicAdd(count, 1u);
 }
@@ -508,6 +510,15 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
     g.cg_pool = c.take<u8>(A * static_cast<size_t>(g.pool_cap));
   };
 
+  // Pass 0 of a hinted batch asks for the common-route-only order of run_build_pass (which grants it where k_graph runs and
+  // every window's sequences fit a queued key): the general kernels are not launched, the windows that need one come back
+  // through the retry pass below.  Everything here is known before the pass -- no counter is read back for it.
+  // MA_NO_CAP_RETRY shows what pass 0 leaves flagged, so it keeps the full order; MA_NO_DEFER is the route switch.
+  // Only for a lane that works beside other lanes (co_lanes > 1): what the mode saves is the general kernels' wait for LDS
+  // next to another lane's kernels -- alone on the chip their idle launches take 0.06 ms, and a re-routed window would pay
+  // a second pass for nothing.  A single lane and a stage called on its own keep the full order.
+  bool const defer_pass0 = b.read_hint != nullptr && !nested && ctx->co_lanes > 1 && !ctx->defer_off && !getenv("MA_NO_CAP_RETRY") &&
+                           !getenv("MA_NO_DEFER");
   if (!nested) ctx->stats[2] += static_cast<unsigned long long>(n);
   // Pass 0 runs every window with the planned capacities.  Windows that come back flagged TABLE_OVERFLOW (graph larger
   // than the node array, walk search larger than the arena: the reference has no such limits) are re-assembled from
@@ -531,11 +542,21 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
     ws.mc_log2 = mc_log2_alloc;
     if (pass > 0) {
       if (getenv("MA_NO_CAP_RETRY")) break;  // tests: show what a pass leaves flagged
-      MA_HIP(ctx, hipMemsetAsync(counters + 10, 0, 4, ctx->stream));
+      MA_HIP(ctx, hipMemsetAsync(counters + 10, 0, 8, ctx->stream));
       hipLaunchKernelGGL(k_reset_overflowed, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, out, win_flags, n, counters + 10);
-      u32 n_over = 0;
-      MA_HIP(ctx, hipMemcpyAsync(&n_over, counters + 10, 4, hipMemcpyDeviceToHost, ctx->stream));
+      u32 host_over[2] = {0, 0};  // windows to re-assemble, and those among them that a common-route-only pass handed over
+      MA_HIP(ctx, hipMemcpyAsync(host_over, counters + 10, 8, hipMemcpyDeviceToHost, ctx->stream));
       MA_HIP(ctx, ma_stream_sync(ctx));
+      u32 const n_over = host_over[0];
+      // A batch that sends more than 1 window in 256 this way (2.5 kb windows, the ladder's upper rungs, large three-sample
+      // graphs) pays k_classify / k_insert / k_support twice for them on every call: the context leaves the mode for good
+      // and pays once.  Below that the retry pass's fixed latency is paid for a handful of windows, as for any overflow.
+      if (pass == 1 && !ctx->defer_off && static_cast<u64>(host_over[1]) * 256u > static_cast<u64>(n)) {
+        ctx->defer_off = true;
+        if (getenv("MA_VERBOSE"))
+          fprintf(stderr, "[microasm] assemble: %u of %d windows needed a general kernel: common-route-only passes off for this context\n",
+                  host_over[1], n);
+      }
       if (n_over == 0) break;
       if (getenv("MA_VERBOSE")) fprintf(stderr, "[microasm] assemble: capacity retry %d for %u windows (nc %u, ac %u)\n", pass, n_over, ws.nc, ws.ac);
     }
@@ -565,7 +586,9 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
       // next k (k_select_active); a second pass only sees the windows whose graph at that k had a cycle / was too complex
       int const rungs = (P.max_k - P.min_k) / P.k_step + 1;
       for (int kpass = 0; kpass <= rungs; ++kpass) {
-        MA_TRY_RC(run_select_active(ctx, ws, win0, nwin, gate_approx, out.win_k, active, counters + 8));
+        // (k_select_active also clears what the pass's build and clean kernels count into: counters + 12 and the chunk's
+        //  per-slot words of this carve -- build.hip)
+        MA_TRY_RC(run_select_active(ctx, ws, win0, nwin, gate_approx, out.win_k, active, counters + 8, counters + 12));
         u32 host_cnt[2] = {0, 0};
         MA_HIP(ctx, hipMemcpyAsync(host_cnt, counters + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
         MA_HIP(ctx, ma_stream_sync(ctx));
@@ -577,6 +600,14 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
           // few windows are left on the ladder: their next rungs at once (speculate_tail), until none is pending
           u32 still = 0;
           MA_TRY_RC(speculate_tail(ctx, b, out, gate_approx, active, static_cast<u32>(ws.n_active), win_flags, counters + 8, &still));
+          // The nested pass works in this chunk's arena and may have GROWN it: DevBuf::reserve frees and allocates anew, and
+          // the chunk's carve then points into freed memory.  No ordinary pass follows, but the next k_select_active clears
+          // the chunk's per-slot words through the carve -- so it is taken again from where the arena lies now (the arena
+          // only grows: it holds this chunk as before).
+          ws.tc_log2 = tc_log2_alloc;
+          ws.mc_log2 = mc_log2_alloc;
+          Carver cw2{static_cast<char*>(ctx->ws_build.p)};
+          carve_ws(cw2, ws, static_cast<size_t>(nwin));
           continue;  // (the next k_select_active moves what is still pending to its next rung, or finds the ladder exhausted)
         }
         if (ws.n_active > 0) {
@@ -589,6 +620,7 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
           if (nested || P.min_k != P.max_k) MA_TRY_RC(run_count_inst(ctx, b, ws, win0, nwin, counters));
           ws.tc_log2 = tc_log2_alloc;
           ws.mc_log2 = mc_log2_alloc;  // run_build_pass shrinks both to what this attempt needs
+          ws.defer_general = (pass == 0 && defer_pass0) ? 1u : 0u;  // (asked for; run_build_pass decides)
           MA_TRY_RC(run_build_pass(ctx, b, ws, counters + 12, tc_log2_alloc));
           if (ctx->collect) {
             unsigned long long* acc = nullptr;

@@ -125,9 +125,25 @@ __global__ __launch_bounds__(kBT) void k_count_inst(DBatch b, GraphWs ws, int wi
 // of the ladder cost twenty passes of mostly idle kernels).  win_k[w] = Graph::CurrentK(): the k attempted last; a window
 // that runs out of ladder ends on its last rung, unresolved, as the reference's loop does.
 __global__ void k_select_active(GraphWs ws, int win0, int nwin, const u32* gate_approx, u32* win_k, u32* active,
-                                u32* n_active, int min_k, int max_k, int k_step) {
+                                u32* n_active, int min_k, int max_k, int k_step, u32* pass_ctr) {
   int const i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nwin) return;
+  // The per-pass clears of the build and clean stages, which were a fill each on the lane's stream.  This kernel runs before
+  // every pass on the pass's stream, over the chunk's own carve of the workspace, with a thread for each of the chunk's nwin
+  // slots (n_active <= nwin).  Last writers, all kernels of the PREVIOUS pass on this stream (or of the nested pass of
+  // speculate_tail, which the host waits for before it comes back here), hence complete:
+  //   n_slow[a]     k_classify (atomicAdd); read by k_insert, k_mm_q's route and k_workload_stats; first reader now: k_classify
+  //   gr_done[a]    k_graph / the general graph kernels; first reader now: k_graph_gen's three phases (k_graph writes its own 0)
+  //   cg_state[a]   k_clean_chains / k_clean_tail; first reader now: k_clean_chains, k_clean_tail and k_clean
+  //   pass_ctr[0:3] max_slow, max_gen[2]: k_classify / k_support (atomic max); first reader now: k_classify, tbl_log2()
+  //   mm_pool_used  k_support (atomicAdd); first reader now: k_support
+  ws.n_slow[i] = 0;
+  ws.gr_done[i] = 0;
+  if (ws.cg_state) ws.cg_state[i] = 0;
+  if (i == 0) {
+    pass_ctr[0] = pass_ctr[1] = pass_ctr[2] = 0;
+    *ws.mm_pool_used = 0ull;
+  }
   int const w = win0 + i;
   if (ws.win_flags[w] & 1u) return;           // done in an earlier pass
   u32 const last = win_k[w];
@@ -1679,7 +1695,12 @@ __global__ __launch_bounds__(kSupT) void k_support(DBatch b, GraphWs ws, u32* ma
     ws.mm_mode[a] = qdedup ? (gen_count | 0x20000000u) : qmode ? (gen_count | 0x40000000u) : (gen_count | (lds_ok ? 0u : 0x80000000u));
     atomic_max_lazy(max_gen, gen_count);
     ws.mm_log2[a] = 0;
-    if (!qmode && !lds_ok && gen_count) {
+    // Common-route-only pass (run_build_pass): a window whose general instances wait for k_mm_q (queued keys), k_mm_lds or
+    // k_mm_hbm -- every window outside dedup mode that has any -- is handed to the retry pass, and takes nothing from the pool.
+    // (Without general instances the table rows are final already, whatever the mode word says: all three kernels leave.)
+    bool const defer = ws.defer_general && !qdedup && gen_count != 0;
+    if (defer) atomicOr(&ws.win_flags[w], 4u | kDeferBit);
+    if (!defer && !qmode && !lds_ok && gen_count) {
       // the window's HBM-resident set: 12 bytes per entry at a load of 3/4, carved out of the chunk's pool.  A pool that is
       // used up is a capacity like any other: the window is flagged and the retry pass, whose pool holds a full set per
       // window, re-assembles it.
@@ -2640,7 +2661,12 @@ __global__ __launch_bounds__(kGrT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   u32 const ninst = ws.win_ninst[w], nref = ninst - ws.win_nread_inst[w];
   u32 const nw = (ws.inst_stride + 31u) / 32u + 1u;
   if (threadIdx.x == 0) ws.gr_done[a] = 0;
-  if ((ws.win_flags[w] & 4u) || tcap > kGrSlots || ninst > ws.inst_stride || ninst >= (1u << 22)) return;  // (uniform)
+  if (ws.win_flags[w] & 4u) return;  // (uniform: the flag was set by an earlier kernel)
+  if (tcap > kGrSlots || ninst > ws.inst_stride || ninst >= (1u << 22)) {  // (uniform) not this kernel's window
+    // common-route-only pass: k_graph_gen is not launched, the retry pass assembles the window
+    if (ws.defer_general && threadIdx.x == 0) atomicOr(&ws.win_flags[w], 4u | kDeferBit);
+    return;
+  }
   const u64* keys = ws.tbl_key + (static_cast<size_t>(a) << tcl);
   const u32* first = ws.tbl_first + (static_cast<size_t>(a) << tcl);
   u32* cnt = ws.tbl_cnt + (static_cast<size_t>(a) << tcl) * CW;
@@ -2765,7 +2791,10 @@ __global__ __launch_bounds__(kGrT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   }
   IPROF_SYNC(17);  // ranks
   if (threadIdx.x == 0) ws.n_nodes[a] = total_nodes;
-  if (total_nodes < ws.nc && total_nodes > kGrSlots) return;  // node indices beyond the packed edge key: the general kernels
+  if (total_nodes < ws.nc && total_nodes > kGrSlots) {  // node indices beyond the packed edge key: the general kernels
+    if (ws.defer_general && threadIdx.x == 0) atomicOr(&ws.win_flags[w], 4u | kDeferBit);  // (... of the retry pass)
+    return;
+  }
   if (total_nodes >= ws.nc) {  // capacity exceeded: flagged (k_rank's rule), the retry passes grow it
     if (threadIdx.x == 0) {
       atomicOr(&ws.win_flags[w], 4u);
@@ -2864,7 +2893,11 @@ __global__ __launch_bounds__(kGrT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     }
   }
   IPROF_SYNC(20);  // edge pass
-  if (l_fail) return;  // (gr_done stays 0: the three general kernels redo this window from the table)
+  if (l_fail) {  // (gr_done stays 0: the three general kernels redo this window from the table)
+    // common-route-only pass: they are not launched -- the retry pass assembles the window from scratch
+    if (ws.defer_general && threadIdx.x == 0) atomicOr(&ws.win_flags[w], 4u | kDeferBit);
+    return;
+  }
   // ---- 5. every distinct edge to its place in its node's list ----
   bool over = false;
   for (u32 i = threadIdx.x; i < kGrSet; i += kGrT) {
@@ -2901,9 +2934,8 @@ int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev,
   size_t const A = ws.n_active;
   ws.tc_log2 = tc_log2_alloc;
   ws.max_slow = counters_dev;
-  MA_HIP(ctx, hipMemsetAsync(counters_dev, 0, 12, ctx->stream));  // max_slow, max_gen[2]
-  MA_HIP(ctx, hipMemsetAsync(ws.n_slow, 0, 4 * A, ctx->stream));
-  MA_HIP(ctx, hipMemsetAsync(ws.mm_pool_used, 0, 8, ctx->stream));
+  // (counters_dev[0:3] -- max_slow, max_gen[2] --, n_slow, mm_pool_used and gr_done are zero here: k_select_active, which
+  //  precedes every build pass on this stream, clears them)
   u32 const tiles_per_win = std::max<u32>(1, (ws.max_reads + 63) / 64);
   u32 const tile_cap = (64 * ws.max_read_len + 32 + 15) & ~15u;
   size_t const lds_c = ((ws.max_ref_len + 8 + 15) & ~15u) + 2048 + 2ull * tile_cap + 2 * 4ull * 64 * classify_mask_words(ws.max_read_len) + 64;
@@ -2925,6 +2957,15 @@ int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev,
   // k_graph takes the common window (and then k_support queues that window's read-support counts for it)
   size_t const lds_g = graph_lds_bytes(ws.inst_stride, ws.ref_stride, S);
   ws.graph_fused = (lds_g <= 120u * 1024u && !getenv("MA_NO_GRAPH_FUSE")) ? 1u : 0u;
+  // COMMON-ROUTE-ONLY PASS (the caller asks for it in ws.defer_general: pass 0 of a hinted batch, assemble.hip).  k_mm_q<14>
+  // and k_graph_gen hold ~80 KB of LDS per workgroup; with nothing to do they take 0.06 ms together alone on the chip, but
+  // beside another lane's kernels every one of their workgroups waits for a CU with that much LDS free (DESIGN.md section 9:
+  // 1.9 ms per lane-step).  The host cannot know whether a window needs them without reading a counter back, so in this mode it
+  // launches none of the general kernels: k_support and k_graph flag a window that needs one (4 | kDeferBit) and the capacity
+  // retry pass, which runs every kernel, assembles it from scratch as it does a window that outgrew a capacity.  Only where
+  // the common route can take every window: k_graph runs, and no window has more sequences than a queued key names.
+  bool const defer = ws.defer_general && ws.graph_fused && ws.max_reads + 1u <= kSeqCap;
+  ws.defer_general = defer ? 1u : 0u;
   // a wavefront's dedup table: the k-mers of two reads of the longest length at a load of 3/4 at most
   ws.dd_log2 = 9;
   while ((1u << ws.dd_log2) / 4u * 3u < 2u * ws.max_read_len && ws.dd_log2 < 12) ++ws.dd_log2;
@@ -2947,18 +2988,21 @@ int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev,
   ctx->toc();
   // windows whose general instances fit an LDS set are finished by k_mm_lds; the HBM-resident sets only hold what the
   // remaining windows routed to them (usually nothing: both kernels then leave at their first test)
-  ctx->tic("k_mm_q");
-  hipLaunchKernelGGL(k_mm_q<14>, dim3(std::min<u32>(static_cast<u32>(ws.n_active), 512u)), dim3(kMmT), 0, ctx->stream, b, ws);
-  ctx->toc();
-  if (ws.max_reads + 1u > kSeqCap) {  // (the scan route is for windows of more sequences than a key's leader index names)
-    ctx->tic("k_mm_lds");
-    if (ws.mm_probe_max < kMmLdsCap) hipLaunchKernelGGL(k_mm_lds<true>, dim3(ws.n_active), dim3(kMmT), 0, ctx->stream, b, ws);
-    else hipLaunchKernelGGL(k_mm_lds<false>, dim3(ws.n_active), dim3(kMmT), 0, ctx->stream, b, ws);
+  // (none of them in a common-route-only pass: k_support flagged the windows that wait for one)
+  if (!defer) {
+    ctx->tic("k_mm_q");
+    hipLaunchKernelGGL(k_mm_q<14>, dim3(std::min<u32>(static_cast<u32>(ws.n_active), 512u)), dim3(kMmT), 0, ctx->stream, b, ws);
+    ctx->toc();
+    if (ws.max_reads + 1u > kSeqCap) {  // (the scan route is for windows of more sequences than a key's leader index names)
+      ctx->tic("k_mm_lds");
+      if (ws.mm_probe_max < kMmLdsCap) hipLaunchKernelGGL(k_mm_lds<true>, dim3(ws.n_active), dim3(kMmT), 0, ctx->stream, b, ws);
+      else hipLaunchKernelGGL(k_mm_lds<false>, dim3(ws.n_active), dim3(kMmT), 0, ctx->stream, b, ws);
+      ctx->toc();
+    }
+    ctx->tic("k_mm_hbm");
+    hipLaunchKernelGGL(k_mm_hbm, dim3(ws.n_active), dim3(kBT), 0, ctx->stream, b, ws);
     ctx->toc();
   }
-  ctx->tic("k_mm_hbm");
-  hipLaunchKernelGGL(k_mm_hbm, dim3(ws.n_active), dim3(kBT), 0, ctx->stream, b, ws);
-  ctx->toc();
   if (getenv("MA_VERBOSE")) {  // (diagnostics only: this does wait for the stream)
     std::vector<u32> mm(A);
     u32 max_gen[2] = {0, 0};
@@ -2980,7 +3024,7 @@ int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev,
             ws.ref_stride, ws.max_reads, sup_cache, xs_log2);
   }
   // node records + edges: k_graph for the common window (table of at most 8192 slots), the three general kernels for the rest
-  MA_HIP(ctx, hipMemsetAsync(ws.gr_done, 0, 4 * A, ctx->stream));
+  // (gr_done is zero: k_select_active cleared it and no kernel above writes it; k_graph writes its windows' own 0 / 1)
   if (ws.graph_fused) {
     if (lds_g > 65536)
       MA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_graph), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2989,10 +3033,12 @@ int run_build_pass(ma_ctx* ctx, const DBatch& b, GraphWs& ws, u32* counters_dev,
     hipLaunchKernelGGL(k_graph, dim3(ws.n_active), dim3(kGrT), lds_g, ctx->stream, b, ws, static_cast<u32>(ctx->prm.min_node_cov));
     ctx->toc();
   }
-  ctx->tic("k_graph_gen");
-  hipLaunchKernelGGL(k_graph_gen, dim3(std::min<u32>(static_cast<u32>(ws.n_active), 512u)), dim3(kRankT), 0, ctx->stream, b, ws,
-                     static_cast<u32>(ctx->prm.min_node_cov));
-  ctx->toc();
+  if (!defer) {  // (common-route-only pass: k_graph flagged what it did not take)
+    ctx->tic("k_graph_gen");
+    hipLaunchKernelGGL(k_graph_gen, dim3(std::min<u32>(static_cast<u32>(ws.n_active), 512u)), dim3(kRankT), 0, ctx->stream, b, ws,
+                       static_cast<u32>(ctx->prm.min_node_cov));
+    ctx->toc();
+  }
   MA_HIP(ctx, hipGetLastError());
   return MA_OK;
 }
@@ -3005,10 +3051,11 @@ int run_count_inst(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, int win0, in
 }
 
 int run_select_active(ma_ctx* ctx, const GraphWs& ws, int win0, int nwin, const u32* gate_approx, u32* win_k,
-                      u32* active, u32* n_active_dev) {
+                      u32* active, u32* n_active_dev, u32* pass_ctr) {
+  // (this fill stays: the kernel's own threads add to the two counters, none of them can clear them for the others)
   MA_HIP(ctx, hipMemsetAsync(n_active_dev, 0, 8, ctx->stream));
   hipLaunchKernelGGL(k_select_active, dim3((nwin + 255) / 256), dim3(256), 0, ctx->stream, ws, win0, nwin,
-                     gate_approx, win_k, active, n_active_dev, ctx->prm.min_k, ctx->prm.max_k, ctx->prm.k_step);
+                     gate_approx, win_k, active, n_active_dev, ctx->prm.min_k, ctx->prm.max_k, ctx->prm.k_step, pass_ctr);
   MA_HIP(ctx, hipGetLastError());
   return MA_OK;
 }

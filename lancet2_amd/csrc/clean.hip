@@ -2734,8 +2734,9 @@ int run_clean_pass(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm
   if (use_chains && ws.cg_state) {
     // the first CompressGraph of every candidate component as bulk-parallel LDS work, then the rest of the candidate loop
     // on the few dozen nodes it leaves; windows it does not take (graph beyond its capacities, unusual shapes) keep
-    // cg_state = 0 and go through k_clean from the raw graph
-    MA_HIP(ctx, hipMemsetAsync(ws.cg_state, 0, sizeof(u32) * static_cast<size_t>(ws.n_active), ctx->stream));
+    // cg_state = 0 and go through k_clean from the raw graph.  (cg_state[0 .. n_active) is zero here: k_select_active, which
+    // precedes every pass on this stream, clears the chunk's slots; the last writers were the previous pass's k_clean_chains /
+    // k_clean_tail, the first readers are the kernels launched below -- build.hip, k_select_active)
     MA_TRY_RC(run_clean_chains(ctx, b, ws, ctx->prm));
     ctx->tic("k_clean_tail");
     hipLaunchKernelGGL((k_clean_tail<TailSmall, true>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
@@ -2746,9 +2747,7 @@ int run_clean_pass(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm
     ctx->tic("k_clean_tail");
     hipLaunchKernelGGL((k_clean_tail<TailHbm, false>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
     ctx->toc();
-  } else if (ws.cg_state) {
-    MA_HIP(ctx, hipMemsetAsync(ws.cg_state, 0, sizeof(u32) * static_cast<size_t>(ws.n_active), ctx->stream));
-  }
+  }  // (without the chains route cg_state stays what k_select_active left: 0, every window is k_clean's)
   if (use_chains && ws.cg_state && getenv("MA_VERBOSE")) {  // which windows fall through to k_clean, and how large they are
     std::vector<u32> st(ws.n_active), nn(ws.n_active), hd(static_cast<size_t>(ws.n_active) * kCgHdr);
     (void)hipMemcpyAsync(st.data(), ws.cg_state, 4 * st.size(), hipMemcpyDeviceToHost, ctx->stream);

@@ -26,6 +26,9 @@ constexpr u32 kInstLast = 1u << 27;
 constexpr u32 kInstFirst = 1u << 26;  // set by k_rank: first instance of a node that survives low-coverage pruning
 constexpr u32 kInstSlotMask = (1u << 26) - 1;
 constexpr int kMaxSamples = 8;
+// win_flags bit beside the overflow bit (4): the window did not outgrow a capacity, a common-route-only pass handed it to
+// the retry pass because it needs a general kernel (GraphWs::defer_general); k_reset_overflowed counts these on their own
+constexpr u32 kDeferBit = 8u;
 
 struct GraphWs {
   // ---- per k attempt ----
@@ -60,6 +63,8 @@ struct GraphWs {
   u32* win_nslots;        // [a] table slots this window uses (<= the stride; 6144 = k_insert's LDS map copied out, else a power of two)
   uint4* slow_rec;        // [a][inst_stride] k_insert: one record per reference k-mer, then per slow-queue entry: id, instance | flags, sequence
   u32 graph_fused;        // k_graph runs in this attempt (then k_support may queue a window's read-support counts for it)
+  u32 defer_general;      // common-route-only pass: k_mm_q / k_mm_lds / k_mm_hbm / k_graph_gen are not launched; a window that
+                          // needs one of them is flagged 4 | kDeferBit and assembled by the capacity retry pass (run_build_pass)
   u32 dd_log2;            // log2 of the entries of a wavefront's dedup table in k_support
   u32* n_genq;            // [a] entries of the window's key / count queue (k_support; the queue lives where slowq did)
   u32* n_edgeq;           // [a] entries of the window's edge queue (k_support; the queue lives where slow_rec did)
@@ -102,7 +107,7 @@ struct GraphWs {
   u32* scratch;           // [a][4 * NC] queues / flat indices / sort buffers
   u32 ac;                 // arena capacity (records)
   uint4* arena;           // [a][AC]
-  u32* win_flags;         // [n_windows] bit0 done, bit1 retry-at-next-k requested
+  u32* win_flags;         // [n_windows] bit0 done, bit1 retry-at-next-k requested, bit2 capacity overflow, bit3 kDeferBit
   int num_samples;
   // ---- compact graph: what the first CompressGraph leaves of the candidate components (k_clean_chains -> k_clean_tail) ----
   u32 vc;                 // node capacity per window (all candidate components together)

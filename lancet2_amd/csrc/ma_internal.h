@@ -83,6 +83,13 @@ struct ma_ctx {
   // nested pass; spec_k = the rung every window of the nested pass is built at (null outside of it)
   ma::DevBuf spec_data, spec_out, spec_nodes;
   const uint32_t* spec_k = nullptr;
+  // common-route-only build passes (assemble.hip: defer_pass0) are off for this context -- a lane is a context of its own --
+  // once one of its calls sent more than 1 window in 256 to the retry pass for a general kernel
+  bool defer_off = false;
+  // (lane) lanes of the ma_process_batch call this context is working for; 1 for a context that runs alone (a single lane,
+  // a stage called on its own).  The common-route-only pass is for lanes > 1: alone on the chip the general kernels' idle
+  // launches cost 0.06 ms, which no re-routed window's second pass is worth
+  int co_lanes = 1;
   // annotation tables (annotate.hip): rebuilt when the GC fraction or max_hap_len changes
   ma::DevBuf ws_cx;
   double cx_gc = -1.0;

@@ -3567,7 +3567,8 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
       ctr = reinterpret_cast<u32*>((reinterpret_cast<uintptr_t>(ctr) + 255) & ~uintptr_t(255));
       ws.pending_ctr = ctr;
       ws.tier_stats = verbose ? ctr + 8 : nullptr;
-      MA_HIP(ctx, hipMemsetAsync(ctr, 0, 64, ctx->stream));
+      // (the persistent kernel's scheduler block lies 256 bytes behind these counters: one fill clears both, below)
+      if (!sched) MA_HIP(ctx, hipMemsetAsync(ctr, 0, 64, ctx->stream));
     }
     MsaArgs args{b, a, o, ws, P, win0, 0u, 0u};
     if (sched) {
@@ -3577,7 +3578,10 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
       u32* const gq = fq + static_cast<size_t>(qcap) * kPoaDoms;
       u32* const hq = gq + static_cast<size_t>(qcap) * kPoaDoms;
       u32 const grid = static_cast<u32>(std::min<size_t>(static_cast<size_t>(nwin), max_workers));
-      MA_HIP(ctx, hipMemsetAsync(S, 0, sizeof(PoaSched), ctx->stream));
+      // One fill for the counter block (64 bytes at pending_ctr, 192 of padding) and the scheduler block behind it, which were
+      // a fill each.  Last writers: the previous chunk's / call's k_poa on this stream (both blocks), or the assembly stage's
+      // kernels, whose arena this is; first readers: k_poa_order does not touch them, k_poa reads and counts into both.
+      MA_HIP(ctx, hipMemsetAsync(ws.pending_ctr, 0, 256 + sizeof(PoaSched), ctx->stream));
       MA_HIP(ctx, hipMemsetAsync(fq, 0xFF, 3 * sizeof(u32) * qcap * kPoaDoms, ctx->stream));
       u32* const order = hq + static_cast<size_t>(qcap) * kPoaDoms;
       hipLaunchKernelGGL(k_poa_order, dim3(1), dim3(1024), 0, ctx->stream, args, order, static_cast<u32>(nwin));
