@@ -4,9 +4,10 @@
 //   extract   WindowBuilder tiles the regions; per window the skip gates (N-only, max-k repeat, inactive region), the read
 //             collector (filters, coverage-capped paired downsampling, comparator) and the coverage gate; the windows that
 //             are left are flattened into batches
-//   engine    ma_prefetch_batch(next) + ma_process_batch(this) (ma_process_stats_batch with --out-vcf): the next batch uploads under this batch's kernels
+//   engine    ma_prefetch_batch(next) + ma_process_batch(this): the next batch uploads under this batch's kernels
+//             (--out-vcf: ONE call, ma_process_cx_batch -- the chain, the FORMAT statistics and the SEQ_CX / GRAPH_CX annotation)
 //             (--packed-reads: the ma_*_packed_batch pair on 4-bit read bases and qualities, half the bytes over the link)
-//             (--read-meta with --out-vcf: ma_prefetch_meta_batch + ma_process_meta_batch on the reads' MAPQ, clip and pair flags,
+//             (--read-meta with --out-vcf: ma_prefetch_meta_batch, and that call with the reads' MAPQ, clip and pair flags,
 //              insert size and start -- RMQ, SCA, FLD, RPCD, MQCD, FSSE are printed too: 24 of 24 FORMAT values)
 //   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
@@ -557,15 +558,15 @@ int main(int argc, char** argv) {
       auto const t0 = Clock::now();
       j.out = std::make_unique<Outputs>();
       j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty(), with_meta);
-      const ma_fmt_out_t* fmt = vcf_path.empty() ? nullptr : &j.out->fmt;  // (null: ma_process_batch)
-      j.rc = with_meta ? ma_process_meta_batch(ctx, packed_reads ? &j.batch->packed_view : &j.batch->view,
-                                               packed_reads ? &j.batch->packed : nullptr, &j.batch->meta, &j.out->gate, &j.out->asmb,
-                                               &j.out->vars, &j.out->geno, fmt, &j.out->fmeta)
-             : packed_reads ? ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb,
-                                                    &j.out->vars, &j.out->geno, fmt)
-                          : ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, fmt);
-      if (j.rc == MA_OK && !vcf_path.empty())  // INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
-        j.rc = ma_annotate_batch(ctx, &j.batch->view, &j.out->asmb, &j.out->vars, gc_frac, &j.out->cx);
+      if (!vcf_path.empty())  // one call: the chain with the statistics and INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
+        j.rc = ma_process_cx_batch(ctx, packed_reads ? &j.batch->packed_view : &j.batch->view, packed_reads ? &j.batch->packed : nullptr,
+                                   with_meta ? &j.batch->meta : nullptr, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
+                                   &j.out->fmt, with_meta ? &j.out->fmeta : nullptr, gc_frac, &j.out->cx);
+      else
+        j.rc = packed_reads ? ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb,
+                                                      &j.out->vars, &j.out->geno, nullptr)
+                            : ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
+                                                     nullptr);  // (null: ma_process_batch)
       if (j.rc != MA_OK) j.err = ma_last_error(ctx);
       busy_engine += secs(Clock::now() - t0);
       to_flush.Push(std::move(j));

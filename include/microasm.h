@@ -19,6 +19,9 @@
  *   ma_genotype_meta_batch / ma_process_meta_batch / ma_prefetch_meta_batch: the calls above + four facts of every read's BAM
  *                             record (ma_read_meta_t) and the six FORMAT statistics over them: RMQ, MQCD, SCA, FLD, RPCD, FSSE
  *                             (caller/variant_support.cpp:184-194, :261-305, :358-363, base/mann_whitney.h:127-225)
+ *   ma_process_cx_batch    <- ma_process_meta_batch + the annotation of ma_annotate_batch as a stage of the chain, where
+ *                             VariantBuilder::ExtractVariants has it (core/variant_builder.cpp:157-160): the whole per-window
+ *                             body in one call
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -360,6 +363,22 @@ int ma_process_meta_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_re
                           const ma_fmt_meta_out_t* fmeta);
 int ma_prefetch_meta_batch(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_reads_t* next_pk /* or NULL */,
                            const ma_read_meta_t* next_meta);
+
+/* ma_process_meta_batch + the annotation of ma_annotate_batch as a stage of the chain (after the MSA, before genotyping, as
+ * in VariantBuilder::ExtractVariants).  cx == NULL, or all four members NULL, IS ma_process_meta_batch: the same kernels,
+ * nothing allocated, gc_frac not read.  Some but not all four members set is MA_ERR_ARG, and so is a NaN gc_frac with cx
+ * wanted; a gc_frac outside [0, 1] is clamped, as in ma_annotate_batch.  The stage reads the engine's own device-side assembly
+ * and variant arrays -- nothing is uploaded for it, and with MA_MEM_HOST a caller may leave hap_bases, hap_runs and any other
+ * optional array out and still get the annotation; only the used variant slots come back (80 bytes each).  In every variant
+ * slot a window uses (slot < win_nvars[w]) the result is byte for byte what ma_annotate_batch returns for the same assembly
+ * and variant arrays and the same gc_frac; what unused slots hold is unspecified.  There is no prefetch call of its own: a
+ * batch queued by ma_prefetch_batch / ma_prefetch_packed_batch / ma_prefetch_meta_batch is computed for what the previous
+ * call asked for -- the four annotation arrays and that call's gc_frac included -- and dropped and computed in the call if
+ * this call asks for other arrays or another gc_frac. */
+int ma_process_cx_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk /* NULL: ASCII */,
+                        const ma_read_meta_t* meta /* or NULL */, const ma_gate_out_t* gate, const ma_asm_out_t* asmb,
+                        const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt,
+                        const ma_fmt_meta_out_t* fmeta, double gc_frac, const ma_cx_out_t* cx);
 
 /* Kernel timing mode: 0 = off, 1 = reset at every API call (default), 2 = accumulate across calls
  * until ma_timing_control is called again (used by bench.py to time kernels over the timed region), 3 = as 2 and

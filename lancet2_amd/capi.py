@@ -114,6 +114,10 @@ class CxOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("seq_cx_i", "seq_cx_f", "seq_cx_d", "graph_cx")]
 
 
+# ma_process_cx_batch(ctx, batch, packed, meta, gate, asm, var, geno, fmt, fmeta, double gc_frac, cx)
+PROCESS_CX_ARGTYPES = [C.c_void_p] * 10 + [C.c_double, C.c_void_p]
+
+
 BATCH_DTYPES = dict(ref_bases=np.uint8, ref_off=np.uint32, read_win_off=np.uint32,
                     read_off=np.uint64, read_bases=np.uint8, read_quals=np.uint8,
                     read_qname_id=np.uint32, read_sample=np.uint8, read_flags=np.uint8, read_hint=np.int32)

@@ -4,8 +4,8 @@
 //   base/longdust_scorer.h:217-462         LongdustQ k-mer concentration score (k=4 flanks, k=7 haplotype)
 //
 // Two kernels, both tiny next to the aligners (one pass over <= 16 haplotypes of <= 4 kb per window):
-//   k_hap_lq  one workgroup per (window, component): LongdustQ(k=7) of the component's REF haplotype, 4^7 count
-//             table in LDS (64 KB), both strands from the same table (count_rc[x] = count_fwd[rc(x)]).
+//   k_hap_lq  one workgroup per (window, component that holds a variant): LongdustQ(k=7) of the component's REF haplotype,
+//             4^7 16-bit counts in LDS (32 KB), both strands from the same table (count_rc[x] = count_fwd[rc(x)]).
 //   k_seqcx   one wavefront per variant: the +-50 window of every (ALT, haplotype) site staged in LDS; lanes
 //             cooperate on the counting passes and evaluate 64 candidate repeat starts at a time.
 // Exactness: every integer feature and every f32/f64 add, multiply and divide follows the reference's operation
@@ -115,25 +115,43 @@ __device__ __forceinline__ f64 q_of(f64 sum_log_fact, u32 valid, const f64* ftab
 // ---- k_hap_lq: LongdustQ(k=7) of each component's REF haplotype ----------------------------------------
 constexpr int kHapK = 7;
 constexpr u32 kHapBins = 1u << (2 * kHapK);
+constexpr u32 kHapWords = kHapBins / 2;  // 16-bit counts, two bins per LDS word: a count is at most max_hap_len - 6 <= 8186
 constexpr int kHlqThreads = 256;
 constexpr u32 kListCap = 2048;  // k-mers with count >= 2 of a haplotype of <= 4096 bases
-// one pad word per 256 bins: the reverse-strand pass reads bins 256 apart across the lanes of a wavefront
-// (rc() moves the last three bases to the front), which would be a 64-way LDS bank conflict unpadded
-__device__ __forceinline__ u32 padded(u32 bin) { return bin + (bin >> 8); }
+// Bin -> LDS word.  Bins 2 j and 2 j + 1 share word j (low and high half).  The reverse-strand pass reads bins 256 apart
+// across the lanes of a wavefront (rc() moves the last three bases to the front): words 128 apart, one bank for all of them
+// unrotated.  Chosen here: no padding but a ROTATION of every 128-word block by rot(f), f = bin >> 8 the block's number --
+// the lanes of that pass differ in f alone, so their banks are (c + rot(f)) for one c.  rot is a bijection of 0 .. 63, and
+// its low five bits are distinct over the 32 values of f that one half of the wavefront holds (those halves differ in bit 1
+// of f, which rot moves to bit 5): no two lanes share a bank whether the read is served per 32 lanes on 32 banks or per 64
+// on 64.  The forward pass reads consecutive bins (two lanes per word, one block, one rotation): conflict free as well.
+__device__ __forceinline__ u32 word_of(u32 bin) {
+  u32 const w = bin >> 1, f = bin >> 8;
+  u32 const rot = ((f & 2u) << 4) | ((f >> 1) & 0x1Eu) | (f & 1u);
+  return (w & ~127u) | ((w + rot) & 127u);
+}
+__device__ __forceinline__ u32 count_of(const u32* cnt, u32 bin) { return (cnt[word_of(bin)] >> (16u * (bin & 1u))) & 0xFFFFu; }
 
 __global__ __launch_bounds__(kHlqThreads) void k_hap_lq(CxArgs A) {
-  __shared__ u32 cnt[kHapBins + (kHapBins >> 8)];
-  __shared__ f64 list[2][kListCap];
+  __shared__ u32 cnt[kHapWords];
+  __shared__ u16 list[2][kListCap];
   __shared__ u32 wave_tot[2][4];
+  __shared__ f64 strand_q[2];
   __shared__ u32 n_valid;
   int const w = blockIdx.x / A.MC, c = blockIdx.x % A.MC;
   u32 const tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
   size_t const ci = static_cast<size_t>(w) * A.MC + c;
-  if (A.v.win_nvars[w] == 0 || static_cast<u32>(c) >= A.a.win_ncomp[w]) return;
+  u32 const nv = min(A.v.win_nvars[w], static_cast<u32>(A.MV));
+  if (nv == 0 || static_cast<u32>(c) >= A.a.win_ncomp[w]) return;
+  {  // a component none of the window's variants lies in: k_seqcx never reads its value
+    int mine = 0;
+    for (u32 i = tid; i < nv; i += kHlqThreads) mine |= A.v.var_comp[static_cast<size_t>(w) * A.MV + i] == static_cast<u32>(c);
+    if (!__syncthreads_or(mine)) return;
+  }
   size_t const hi = static_cast<size_t>(w) * A.MH + A.a.comp_hap0[ci];
   u32 const L = A.a.hap_len[hi];
   const u8* s = A.a.hap_bases + hi * A.ML;
-  for (u32 i = tid; i < kHapBins + (kHapBins >> 8); i += kHlqThreads) cnt[i] = 0;
+  for (u32 i = tid; i < kHapWords; i += kHlqThreads) cnt[i] = 0;
   if (tid == 0) n_valid = 0;
   __syncthreads();
   u32 mine = 0;
@@ -147,7 +165,7 @@ __global__ __launch_bounds__(kHlqThreads) void k_hap_lq(CxArgs A) {
       code = (code << 2) | (b & 3u);
     }
     if (ok) {
-      atomicAdd(&cnt[padded(code)], 1u);
+      atomicAdd(&cnt[word_of(code)], 1u << (16u * (code & 1u)));  // (no carry into the other half: see kHapWords)
       mine++;
     }
   }
@@ -159,13 +177,12 @@ __global__ __launch_bounds__(kHlqThreads) void k_hap_lq(CxArgs A) {
     if (tid == 0) A.comp_hlq[ci] = 0.0;  // log1p(max(0, 0))
     return;
   }
-  // ordered compaction of lgamma(count + 1) over the bins with count >= 2, forward and reverse-strand index order;
-  // wave wv owns bins [4096 wv, 4096 wv + 4096)
+  // ordered compaction of the counts >= 2, forward and reverse-strand index order; wave wv owns bins [4096 wv, 4096 wv + 4096)
   for (int strand = 0; strand < 2; ++strand) {
     u32 tot = 0;
     for (u32 it = 0; it < 64; ++it) {
       u32 const idx = wv * 4096u + it * 64u + lane;
-      u32 const cc = cnt[padded(strand ? rc_code(idx, kHapK) : idx)];
+      u32 const cc = count_of(cnt, strand ? rc_code(idx, kHapK) : idx);
       tot += static_cast<u32>(__popcll(__ballot(cc >= 2u)));
     }
     if (lane == 0) wave_tot[strand][wv] = tot;
@@ -176,26 +193,32 @@ __global__ __launch_bounds__(kHlqThreads) void k_hap_lq(CxArgs A) {
     for (u32 k = 0; k < wv; ++k) off += wave_tot[strand][k];
     for (u32 it = 0; it < 64; ++it) {
       u32 const idx = wv * 4096u + it * 64u + lane;
-      u32 const cc = cnt[padded(strand ? rc_code(idx, kHapK) : idx)];
+      u32 const cc = count_of(cnt, strand ? rc_code(idx, kHapK) : idx);
       u64 const m = __ballot(cc >= 2u);
       if (cc >= 2u) {
         u32 const at = off + static_cast<u32>(__popcll(m & ((1ull << lane) - 1ull)));
-        if (at < kListCap) list[strand][at] = A.t.lgam[cc];
+        if (at < kListCap) list[strand][at] = static_cast<u16>(cc);
       }
       off += static_cast<u32>(__popcll(m));
     }
   }
   __syncthreads();
-  if (tid == 0) {
-    f64 sc[2];
-    for (int strand = 0; strand < 2; ++strand) {
-      u32 const n = min(wave_tot[strand][0] + wave_tot[strand][1] + wave_tot[strand][2] + wave_tot[strand][3], kListCap);
-      f64 sum = 0.0;
-      for (u32 i = 0; i < n; ++i) sum += list[strand][i];
-      sc[strand] = q_of(sum, valid, A.t.f7);
+  // the sum of lgamma(count + 1) in list order, one strand per wave: 64 lanes look their terms up at once, then every lane adds
+  // the same 64 values in ascending order (as flank_lq does) -- the terms and the order of the additions of a serial loop
+  if (wv < 2) {
+    u32 const n = __builtin_amdgcn_readfirstlane(
+        min(wave_tot[wv][0] + wave_tot[wv][1] + wave_tot[wv][2] + wave_tot[wv][3], kListCap));
+    f64 sum = 0.0;
+    for (u32 base = 0; base < n; base += 64) {
+      u32 const i = base + lane;
+      f64 const v = i < n ? A.t.lgam[list[wv][i]] : 0.0;
+      u32 const m = min(64u, n - base);
+      for (u32 l = 0; l < m; ++l) sum += read_lane_f64(v, l);
     }
-    A.comp_hlq[ci] = log1p(fmax(0.0, fmax(sc[0], sc[1])));
+    if (lane == 0) strand_q[wv] = q_of(sum, valid, A.t.f7);
   }
+  __syncthreads();
+  if (tid == 0) A.comp_hlq[ci] = log1p(fmax(0.0, fmax(strand_q[0], strand_q[1])));
 }
 
 // ---- k_seqcx: one wavefront per variant ------------------------------------------------------------------

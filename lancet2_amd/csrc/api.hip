@@ -240,7 +240,8 @@ void advance_fields(S* s, const std::vector<OutField>& per_unit, size_t first, s
 
 // One contiguous window range [w0, w1) of the batch on a child context.  All pointers are device pointers.
 int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, const DPacked* pk, int w0, int w1, u32 r0, u32 r1, ma_gate_out_t g,
-             ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, ma_fmt_out_t f, ma_fmt_meta_out_t fm, int lane_index) {
+             ma_asm_out_t a, ma_var_out_t v, ma_geno_out_t q, ma_fmt_out_t f, ma_fmt_meta_out_t fm, ma_cx_out_t cx, double gc_frac,
+             int lane_index) {
   MA_HIP(ch, hipSetDevice(ch->device));
   MA_HIP(ch, hipStreamWaitEvent(ch->stream, start, 0));
   (void)lane_index;  // (starting the lanes a few ms apart was measured: every ms of stagger is lost, the lanes do overlap)
@@ -276,10 +277,12 @@ int run_lane(ma_ctx* ch, hipEvent_t start, const DBatch& full, const DPacked* pk
   advance_fields(&q, gf, 6, 8, w0);   // PL, GQ: per window
   advance_fields(&f, fmt_fields(p, 1), 0, 99, w0);  // (all null without the statistics)
   advance_fields(&fm, fmeta_fields(p, 1), 0, 99, w0);
+  advance_fields(&cx, cx_fields(p, 1), 0, 99, w0);  // (all null without the annotation)
   if (pk) MA_TRY_RC(launch_unpack(ch, *pk, d.read_off, r0, static_cast<u64>(r1) - r0));  // a packed call: the lane's reads first
   MA_TRY_RC(launch_gate(ch, d, g.max_approx, g.max_exact));
   MA_TRY_RC(launch_assemble(ch, d, a, g.max_approx));
   MA_TRY_RC(launch_msa(ch, d, a, v));
+  if (cx.seq_cx_i) MA_TRY_RC(launch_annotate(ch, d, a, v, gc_frac, cx));  // the lane's own tables (ws_cx of the child context)
   MA_TRY_RC(launch_genotype(ch, d, a, v, q, &f, &fm));
   MA_HIP(ch, hipEventRecord(ch->lane_done, ch->stream));
   return MA_OK;
@@ -343,7 +346,8 @@ struct DevLanePool {
 };
 
 int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk, const ma_gate_out_t& g, const ma_asm_out_t& a,
-                     const ma_var_out_t& v, const ma_geno_out_t& q, const ma_fmt_out_t& f, const ma_fmt_meta_out_t& fm) {
+                     const ma_var_out_t& v, const ma_geno_out_t& q, const ma_fmt_out_t& f, const ma_fmt_meta_out_t& fm,
+                     const ma_cx_out_t& cx, double gc_frac) {
   while (static_cast<int>(ctx->lanes.size()) < lanes) {
     ma_ctx* ch = new (std::nothrow) ma_ctx();
     if (!ch) return MA_ERR_NOMEM;
@@ -375,7 +379,7 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk,
   }
   if (!ctx->dev_pool) ctx->dev_pool = new DevLanePool();
   static_cast<DevLanePool*>(ctx->dev_pool)->run(lanes, [&](int k) {
-    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, pk, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, fm, k);
+    rc[k] = run_lane(ctx->lanes[k], ctx->lane_done, d, pk, wb[k], wb[k + 1], rb[k], rb[k + 1], g, a, v, q, f, fm, cx, gc_frac, k);
   });
   for (int k = 0; k < lanes; ++k) {
     if (rc[k] != MA_OK) {
@@ -407,6 +411,7 @@ struct LaneOut {
   ma_geno_out_t q{};
   ma_fmt_out_t f{};
   ma_fmt_meta_out_t m{};
+  ma_cx_out_t c{};
 };
 
 int ensure_pinned(ma_ctx* ch, int set, size_t bytes) {
@@ -433,7 +438,7 @@ int alloc_fields(ma_ctx* ch, S* dev, const std::vector<OutField>& f, size_t stag
   return MA_OK;
 }
 
-// The output arrays of the route, as tables: which struct (0 gate, 1 asm, 2 var, 3 geno, 4 fmt, 5 fmeta) and member, bytes per window.
+// The output arrays of the route, as tables: which struct (0 gate, 1 asm, 2 var, 3 geno, 4 fmt, 5 fmeta, 6 cx) and member, bytes per window.
 struct DenseDesc { int strct; size_t off; size_t win_bytes; };  // small per-window arrays: copied whole
 struct SegDesc { int strct; size_t off; size_t win_stride, unit; u32 kind; };  // packed: only what a window uses
 std::vector<DenseDesc> dense_table(const ma_params_t& p) {
@@ -446,6 +451,11 @@ std::vector<DenseDesc> dense_table(const ma_params_t& p) {
           {1, off_of(&ma_asm_out_t::hap_len), 4 * MH}, {1, off_of(&ma_asm_out_t::hap_nruns), 4 * MH},
           {1, off_of(&ma_asm_out_t::hap_stats), 48 * MH}, {2, off_of(&ma_var_out_t::win_nvars), 4}};
 }
+// The array mask of a job (HostJob::mask, seg_mask_of) is a u32 with bit i = entry i: the 31 entries use bits 0 .. 30, and the
+// next array that is added needs a wider mask.
+constexpr int kSegEntries = 31;
+static_assert(kSegEntries <= 32, "the array mask is a u32");
+static_assert(kSegEntries <= static_cast<int>(sizeof(PackArgs::seg) / sizeof(PackSeg)), "PackArgs::seg is too small for seg_table");
 std::vector<SegDesc> seg_table(const ma_params_t& p) {
   size_t const MH = p.max_haps, MV = p.max_vars, MA_ = p.max_alts, S = p.num_samples, ML = p.max_hap_len, MR = p.max_runs,
                MP = p.max_allele_bytes;
@@ -453,7 +463,7 @@ std::vector<SegDesc> seg_table(const ma_params_t& p) {
   auto var = [&](int strct, size_t off, size_t elem, size_t per_var) {
     return SegDesc{strct, off, MV * per_var * elem, per_var * elem, PK_VAR};
   };
-  return {{1, off_of(&ma_asm_out_t::hap_bases), MH * ML, ML, PK_HAP_BASES},
+  SegDesc const t[] = {{1, off_of(&ma_asm_out_t::hap_bases), MH * ML, ML, PK_HAP_BASES},
           {1, off_of(&ma_asm_out_t::hap_runs), MH * MR * 8, MR * 8, PK_HAP_RUNS},
           var(2, off_of(&ma_var_out_t::var_comp), 4, 1), var(2, off_of(&ma_var_out_t::var_pos), 4, 1),
           var(2, off_of(&ma_var_out_t::var_ref_start), 4, 1), var(2, off_of(&ma_var_out_t::var_ref_off), 4, 1),
@@ -469,13 +479,20 @@ std::vector<SegDesc> seg_table(const ma_params_t& p) {
           var(4, off_of(&ma_fmt_out_t::fmt_cmlod), 8, S * MA_), var(4, off_of(&ma_fmt_out_t::fmt_stat), 8, S * 4),
           // entries 23 .. 26: the statistics over the read metadata (kSegMeta0)
           var(5, off_of(&ma_fmt_meta_out_t::ev_meta), 8, S * (MA_ + 1) * 4), var(5, off_of(&ma_fmt_meta_out_t::ev_rpcd), 8, S * 4),
-          var(5, off_of(&ma_fmt_meta_out_t::fmt_rmq), 8, S * (MA_ + 1)), var(5, off_of(&ma_fmt_meta_out_t::fmt_mstat), 8, S * 5)};
+          var(5, off_of(&ma_fmt_meta_out_t::fmt_rmq), 8, S * (MA_ + 1)), var(5, off_of(&ma_fmt_meta_out_t::fmt_mstat), 8, S * 5),
+          // entries 27 .. 30: the annotation (kSegCx0): 80 bytes per used variant slot
+          var(6, off_of(&ma_cx_out_t::seq_cx_i), 4, 4), var(6, off_of(&ma_cx_out_t::seq_cx_f), 4, 4),
+          var(6, off_of(&ma_cx_out_t::seq_cx_d), 8, 3), var(6, off_of(&ma_cx_out_t::graph_cx), 8, 3)};
+  static_assert(sizeof(t) / sizeof(t[0]) == kSegEntries, "seg_table and kSegEntries disagree");
+  return std::vector<SegDesc>(t, t + kSegEntries);
 }
 constexpr int kSegFmt0 = 19;   // seg_table: first entry of the statistics
 constexpr int kSegMeta0 = 23;  // ... and of those over the read metadata
+constexpr int kSegCx0 = 27;    // ... and of the annotation
 constexpr u32 kSegMetaMask = 0xFu << kSegMeta0;
-struct OutPtrs {  // the six output structs of a call, by table index (the last two, the statistics, may be null)
-  const void* s[6];
+constexpr u32 kSegCxMask = 0xFu << kSegCx0;
+struct OutPtrs {  // the seven output structs of a call, by table index (the last three -- statistics, annotation -- may be null)
+  const void* s[7];
   void* at(int strct, size_t off) const { return s[strct] ? ptr_at(s[strct], off) : nullptr; }
 };
 // which packed arrays the caller asked for (bit i = entry i of seg_table)
@@ -670,6 +687,7 @@ struct HostJob {
   bool timing = false, accumulate = false, collect = false;
   double hbm_share = 1.0;
   u32 mask = 0;                       // seg_table entries to compute and pack
+  double gc_frac = 0.0;               // the annotation's GC fraction (read when the mask holds the annotation's entries)
   std::shared_ptr<UploadTask> upload; // the upload ma_prefetch_batch started (null: every lane uploads its slice)
   std::vector<DBatch> staged;         // the lanes' device views of that upload
   bool packed = false;                // a packed batch: `pk` is a copy of the caller's struct, staged_pk the lanes' views
@@ -705,6 +723,7 @@ struct HostAsync {
   std::thread uploader;
   u32 last_mask = 0;                  // what the last call asked for: a job queued ahead computes the same
   bool have_mask = false;
+  double last_gc = 0.0;               // ... and the GC fraction it annotated with
   std::vector<std::pair<const char*, float>> times;  // kernel timers of the delivered jobs (ma_last_kernel_times)
 };
 HostAsync* async_of(ma_ctx* ctx) {
@@ -779,6 +798,10 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     std::vector<bool> need_m(mf.size(), false);
     for (size_t i = 0; i < mf.size(); ++i) need_m[i] = (job.mask >> (kSegMeta0 + i)) & 1u;
     MA_TRY_RC(alloc_fields(ch, &o.m, mf, 48, need_m));
+    std::vector<OutField> const cf = cx_fields(p, n);
+    std::vector<bool> need_c(cf.size(), false);  // the annotation, likewise
+    for (size_t i = 0; i < cf.size(); ++i) need_c[i] = (job.mask >> (kSegCx0 + i)) & 1u;
+    MA_TRY_RC(alloc_fields(ch, &o.c, cf, 40, need_c));
   }
   if (job.packed) MA_TRY_RC(launch_unpack(ch, dpk, d.read_off, r0, nr));  // after the slice's copies, before the gate
   t_up = since();
@@ -787,11 +810,13 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   MA_TRY_RC(launch_assemble(ch, d, o.a, o.g.max_approx));
   t_asm = since();
   MA_TRY_RC(launch_msa(ch, d, o.a, o.v));
+  // the annotation reads the lane's own assembly and variant arrays, which exist whatever the caller asked for: nothing is uploaded
+  if (job.mask & kSegCxMask) MA_TRY_RC(launch_annotate(ch, d, o.a, o.v, job.gc_frac, o.c));
   t_msa = since();
   MA_TRY_RC(launch_genotype(ch, d, o.a, o.v, o.q, &o.f, &o.m));
   t_geno = since();
   // ---- results: the small dense arrays whole, the rest as packed records, all into the landing area ----
-  OutPtrs const dev{{&o.g, &o.a, &o.v, &o.q, &o.f, &o.m}};
+  OutPtrs const dev{{&o.g, &o.a, &o.v, &o.q, &o.f, &o.m, &o.c}};
   size_t const N = n, MH = p.max_haps, MV = p.max_vars, MCG = p.max_cigar;
   std::vector<DenseDesc> const dense = dense_table(p);
   PackArgs D{};
@@ -1073,7 +1098,7 @@ void forget_views(ma_ctx* ctx) {
 // queue the lanes' jobs of batch `b`, whose inputs are (being) staged in `set` when `ready`
 std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, int set,
                                      std::shared_ptr<UploadTask> upload, u32 mask, const ma_geno_out_t* taps,
-                                     const ma_read_meta_t* meta) {
+                                     const ma_read_meta_t* meta, double gc_frac) {
   HostAsync* ha = async_of(ctx);
   auto job = std::make_shared<HostJob>();
   job->batch = *b;
@@ -1087,6 +1112,7 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
   job->collect = ctx->collect;
   job->hbm_share = ctx->hbm_share / lanes;
   job->mask = mask;
+  job->gc_frac = gc_frac;
   job->upload = upload;
   if (upload) job->staged = views_of(ctx).d[set];
   if (pk) {
@@ -1113,10 +1139,11 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
 
 int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_read_meta_t* meta,
                  const ma_gate_out_t* g, const ma_asm_out_t* a, const ma_var_out_t* v, const ma_geno_out_t* q,
-                 const ma_fmt_out_t* f, const ma_fmt_meta_out_t* fm) {
+                 const ma_fmt_out_t* f, const ma_fmt_meta_out_t* fm, const ma_cx_out_t* cx, double gc_frac) {
   MA_TRY_RC(ensure_workers(ctx, lanes));
   HostAsync* ha = async_of(ctx);
-  OutPtrs const user{{g, a, v, q, f, fm}};
+  OutPtrs const user{{g, a, v, q, f, fm, cx}};
+  if (!cx) gc_frac = 0.0;  // (not read without the annotation: jobs then compare equal whatever the caller passed)
   u32 const mask = seg_mask_of(ctx->prm, user);
   bool const taps = wants_taps(q);
   // did ma_prefetch_batch upload this batch?  (the oldest set that holds it); otherwise any set that holds nothing
@@ -1155,15 +1182,16 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
     }
   }
   std::shared_ptr<HostJob> job = ha->jobs[set];
-  if (job && (job->mask != mask || taps || std::memcmp(&job->prm, &ctx->prm, sizeof(ma_params_t)) != 0 ||
+  if (job && (job->mask != mask || std::memcmp(&job->gc_frac, &gc_frac, sizeof(double)) != 0 || taps || std::memcmp(&job->prm, &ctx->prm, sizeof(ma_params_t)) != 0 ||
               job->timing != ctx->timing || job->accumulate != ctx->accumulate || job->collect != ctx->collect)) {
     job->wait_all();  // queued ahead under other assumptions than this call's: computed again below, from the staged inputs
     job.reset();
   }
   if (!prefetched) ha->uploads[set].reset();
-  if (!job) job = submit_host(ctx, lanes, b, pk, set, prefetched ? ha->uploads[set] : nullptr, mask, taps ? q : nullptr, meta);
+  if (!job) job = submit_host(ctx, lanes, b, pk, set, prefetched ? ha->uploads[set] : nullptr, mask, taps ? q : nullptr, meta, gc_frac);
   ha->jobs[set] = job;
   ha->last_mask = mask;
+  ha->last_gc = gc_frac;
   ha->have_mask = true;
   job->wait_all();
   if (!ctx->accumulate) ha->times.clear();
@@ -1583,7 +1611,8 @@ static int prefetch_any(ma_ctx_t* ctx, const ma_batch_t* next, const ma_packed_r
   // (a batch without read metadata cannot compute the statistics over it: queued without them -- and computed again, from a
   //  fresh upload, if the call then wants them)
   if (ha->have_mask && !ctx->collect)
-    ha->jobs[set] = submit_host(ctx, lanes, next, pk, set, task, meta ? ha->last_mask : ha->last_mask & ~kSegMetaMask, nullptr, meta);
+    ha->jobs[set] = submit_host(ctx, lanes, next, pk, set, task, meta ? ha->last_mask : ha->last_mask & ~kSegMetaMask, nullptr, meta,
+                                ha->last_gc);
   return MA_OK;
 }
 
@@ -1656,10 +1685,17 @@ static int stage_packed(ma_ctx* ctx, const ma_batch_t* b, const ma_packed_reads_
 
 static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_gate_out_t* gate,
                        const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno, const ma_fmt_out_t* fmt,
-                       const ma_read_meta_t* meta = nullptr, const ma_fmt_meta_out_t* fmeta = nullptr) {
+                       const ma_read_meta_t* meta = nullptr, const ma_fmt_meta_out_t* fmeta = nullptr,
+                       const ma_cx_out_t* cx = nullptr, double gc_frac = 0.0) {
   MA_BEGIN(ctx);
   if (!gate || !asmb || !vars || !geno) return MA_ERR_ARG;
   MA_TRY(check_meta(&meta, &fmeta));
+  if (cx) {  // the annotation: all four arrays or none (none IS the call without it, and gc_frac is not read)
+    int const set = (cx->seq_cx_i != nullptr) + (cx->seq_cx_f != nullptr) + (cx->seq_cx_d != nullptr) + (cx->graph_cx != nullptr);
+    if (set != 0 && set != 4) return MA_ERR_ARG;
+    if (set == 0) cx = nullptr;
+    else if (!(gc_frac == gc_frac)) return MA_ERR_ARG;  // NaN
+  }
   if (!gate->max_approx || !gate->max_exact || !geno->allele_counts || !geno->var_qual) return MA_ERR_ARG;
   if (ctx->memspace == MA_MEM_HOST && !getenv("MA_HOST_LEGACY")) {
     // the host route: every lane uploads its own slice, computes, and brings back packed records (see process_host).
@@ -1669,7 +1705,7 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
     if (!asmb->win_status || !asmb->win_ncomp || !asmb->comp_hap0 || !asmb->comp_nhaps || !asmb->hap_len ||
         !asmb->hap_nruns || !vars->win_nvars)
       return MA_ERR_ARG;
-    return process_host(ctx, host_lanes(ctx, b->n_windows), b, pk, meta, gate, asmb, vars, geno, fmt, fmeta);
+    return process_host(ctx, host_lanes(ctx, b->n_windows), b, pk, meta, gate, asmb, vars, geno, fmt, fmeta, cx, gc_frac);
   }
   DBatch d;
   DPacked dp{};
@@ -1694,6 +1730,8 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
   MA_TRY(f.prepare(ctx, fmt, fmt_fields(ctx->prm, d.n_windows), 44, false));
   OutMirror<ma_fmt_meta_out_t> fm;
   MA_TRY(fm.prepare(ctx, fmeta, fmeta_fields(ctx->prm, d.n_windows), 48, false));
+  OutMirror<ma_cx_out_t> c;  // (cx null: all members null, the chain without the annotation)
+  MA_TRY(c.prepare(ctx, cx, cx_fields(ctx->prm, d.n_windows), 40, false));
   // Automatic: three lanes for big batches -- the process has four hardware queues by default (ROCm's GPU_MAX_HW_QUEUES) and a
   // fourth lane would share one with the caller's stream (measured: -18 %); a host that raises GPU_MAX_HW_QUEUES to >= 6
   // before HIP starts gets four (+2 %).
@@ -1710,9 +1748,10 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
     MA_TRY(launch_gate(ctx, d, g.dev.max_approx, g.dev.max_exact));
     MA_TRY(launch_assemble(ctx, d, a.dev, g.dev.max_approx));
     MA_TRY(launch_msa(ctx, d, a.dev, v.dev));
+    if (cx) MA_TRY(launch_annotate(ctx, d, a.dev, v.dev, gc_frac, c.dev));  // where the reference has it (variant_builder.cpp:157-160)
     MA_TRY(launch_genotype(ctx, d, a.dev, v.dev, q.dev, &f.dev, &fm.dev));
   } else {
-    MA_TRY(process_in_lanes(ctx, lanes, d, pk ? &dp : nullptr, g.dev, a.dev, v.dev, q.dev, f.dev, fm.dev));
+    MA_TRY(process_in_lanes(ctx, lanes, d, pk ? &dp : nullptr, g.dev, a.dev, v.dev, q.dev, f.dev, fm.dev, c.dev, gc_frac));
   }
   MA_TRY(g.download(ctx));
   MA_TRY(a.download(ctx));
@@ -1720,8 +1759,17 @@ static int process_any(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads
   MA_TRY(q.download(ctx));
   MA_TRY(f.download(ctx));
   MA_TRY(fm.download(ctx));
+  MA_TRY(c.download(ctx));
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
   return MA_OK;
+}
+
+int ma_process_cx_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_read_meta_t* meta,
+                        const ma_gate_out_t* gate, const ma_asm_out_t* asmb, const ma_var_out_t* vars, const ma_geno_out_t* geno,
+                        const ma_fmt_out_t* fmt, const ma_fmt_meta_out_t* fmeta, double gc_frac, const ma_cx_out_t* cx) {
+  if (!ctx) return MA_ERR_ARG;
+  if (pk) MA_TRY(check_packed(b, pk));
+  return process_any(ctx, b, pk, gate, asmb, vars, geno, fmt, meta, fmeta, cx, gc_frac);
 }
 
 int ma_process_meta_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_packed_reads_t* pk, const ma_read_meta_t* meta,

@@ -29,7 +29,7 @@ struct PackArgs {
   const u32* alt_len;
   u32 MC, MH, MV, MA, MP;
   u32 nseg;
-  PackSeg seg[28];  // (api.hip: seg_table has 27 entries)
+  PackSeg seg[32];  // (api.hip: seg_table has 31 entries, kSegEntries; the array mask of a job is a u32)
 };
 
 // whole-array copies of k_pack_dense (sizes in bytes, multiples of 4)

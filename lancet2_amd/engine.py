@@ -43,6 +43,8 @@ def load_library(path=None):
         lib.ma_genotype_meta_batch.argtypes = [C.c_void_p] * 8
         lib.ma_process_meta_batch.argtypes = [C.c_void_p] * 10
         lib.ma_prefetch_meta_batch.argtypes = [C.c_void_p] * 4
+    if hasattr(lib, "ma_process_cx_batch"):  # (likewise: a build of before the annotation became a stage of the chain)
+        lib.ma_process_cx_batch.argtypes = capi.PROCESS_CX_ARGTYPES
     lib.ma_annotate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.ma_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     lib.ma_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
@@ -195,6 +197,25 @@ class Engine:
                                  capi.fill_struct(capi.FmtOut, f), capi.fill_struct(capi.FmtMetaOut, fm))
         return g, a, v, q, f, fm
 
+    def process_cx(self, arrs, n, nr, meta=None, packed=None, gc_frac=0.41, debug=False, fields=None, meta_fields=None):
+        """ma_process_cx_batch: process_meta() + the annotation of annotate() as a stage of the chain.  `meta` None: without the
+        statistics over the read metadata (fmeta comes back empty).  fmt / fmeta are passed as NULL when they hold no array.
+        Returns (gate, asm, var, geno, fmt, fmeta, cx)."""
+        g = self._alloc(capi.gate_out_spec(n))
+        a = self._alloc(capi.asm_out_spec(self.p, n))
+        v = self._alloc(capi.var_out_spec(self.p, n))
+        q = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))
+        f, fm = self._fmt_pair(n, fields, meta_fields if meta is not None else ())
+        cx = self._alloc(capi.cx_out_spec(self.p, n))
+        b = capi.make_batch_struct(capi.packed_batch_arrays(arrs) if packed is not None else arrs, n, nr)
+        pk = capi.make_packed_struct(packed) if packed is not None else None
+        m = capi.fill_struct(capi.ReadMeta, meta) if meta is not None else None
+        self.process_cx_device(b, pk, m, capi.fill_struct(capi.GateOut, g), capi.fill_struct(capi.AsmOut, a),
+                               capi.fill_struct(capi.VarOut, v), capi.fill_struct(capi.GenoOut, q),
+                               capi.fill_struct(capi.FmtOut, f) if f else None,
+                               capi.fill_struct(capi.FmtMetaOut, fm) if fm else None, capi.fill_struct(capi.CxOut, cx), gc_frac)
+        return g, a, v, q, f, fm, cx
+
     def annotate(self, arrs, n, nr, asm, var, gc_frac=0.41):
         """VariantAnnotator (core/variant_annotator.cpp:43-101): SEQ_CX + GRAPH_CX of every variant."""
         out = self._alloc(capi.cx_out_spec(self.p, n))
@@ -286,6 +307,13 @@ class Engine:
         self._check(self.lib.ma_process_meta_batch(self.h, C.byref(batch_struct), ref(packed_struct), ref(meta_struct),
                                                    C.byref(gate), C.byref(asm), C.byref(var), C.byref(geno), ref(fmt), ref(fmeta)),
                     "ma_process_meta_batch")
+
+    def process_cx_device(self, batch_struct, packed_struct, meta_struct, gate, asm, var, geno, fmt, fmeta, cx, gc_frac=0.41):
+        """ma_process_cx_batch on caller-made structs (either memory space); None: a null pointer"""
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        self._check(self.lib.ma_process_cx_batch(self.h, C.byref(batch_struct), ref(packed_struct), ref(meta_struct),
+                                                 C.byref(gate), C.byref(asm), C.byref(var), C.byref(geno), ref(fmt), ref(fmeta),
+                                                 C.c_double(gc_frac), ref(cx)), "ma_process_cx_batch")
 
     def prefetch_meta(self, batch_struct, packed_struct, meta_struct):
         """MA_MEM_HOST: ma_prefetch_meta_batch -- prefetch() for the batch the next process_meta_device() call brings; the
