@@ -56,7 +56,7 @@ enum ma_memspace { MA_MEM_HOST = 0, MA_MEM_DEVICE = 1 };
 enum ma_wstatus {
   MA_W_NO_HAPLOTYPE = 1u << 0,   /* SKIPPED_NOASM_HAPLOTYPE: no ALT haplotype at any k */
   MA_W_HAP_OVERFLOW = 1u << 1,   /* more haplotypes / components than max_haps / max_comps */
-  MA_W_LEN_OVERFLOW = 1u << 2,   /* haplotype longer than max_hap_len or more runs than max_runs */
+  MA_W_LEN_OVERFLOW = 1u << 2,   /* haplotype longer than max_hap_len, or than the POA stage takes (poa.hip: poa_max_hap_len, printed under MA_VERBOSE), or more runs than max_runs */
   MA_W_BFS_LIMIT = 1u << 3,      /* MaxFlow::HitTraversalLimit (max_flow.h:69) in some component */
   MA_W_TABLE_OVERFLOW = 1u << 4, /* k-mer table / edge list / search arena capacity exceeded, or the traversal cap fell where
                                     the folded walk search cannot place it: the window's result is not the reference's */

@@ -115,6 +115,7 @@ struct ma_ctx {
   hipStream_t hi_stream = nullptr;  // a lane's POA rounds run here, at the greatest stream priority (poa.hip: launch_msa)
   hipEvent_t hi_ev = nullptr;
   bool hi_failed = false;
+  int poa_all32 = -1;       // MA_POA_FORCE_LAB32, read at the context's first POA call (-1: not yet)
   double hbm_share = 1.0;   // fraction of the device this context plans its workspaces for
   hipEvent_t sync_ev = nullptr;  // blocking-sync event: host threads sleep instead of spinning while the stream drains
   // host route (MA_MEM_HOST) of ma_process_batch, per lane: packed result records (pack.hip) and their pinned landing area

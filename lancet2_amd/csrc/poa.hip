@@ -78,6 +78,9 @@ struct PoaWs {
   u32 lean;          // band tiers run poa_fill_lean (default) / poa_fill_band (MA_POA_LEAN=0; same codes, tested)
   u32 lab32;         // this pass runs the kernels with 32-bit label masks (components of 17 .. 32 haplotypes)
   u32 pass;          // 0: every window; 1: only windows whose components all hold <= 16 haplotypes; 2: only the others
+  // The batch holds windows that k_msa_maxima flagged MA_W_LEN_OVERFLOW (else len_cap16 = 0): its two caps and `all32`, so
+  // that every pass steps over exactly the windows it flagged (window_too_long: one predicate for both)
+  u32 len_cap16, len_cap32, len_all32;
   size_t code_cells; // bytes per decision-code plane of a window's OWN area: band fills ((pn + 2) rows x 256 columns at most)
   size_t row_cells;  // i32 per window: row_slots stored rows x 3 matrices x band_stride
   // The full row-synchronous fill (the last tier: an alignment whose 256-column band failed its certificate) needs whole
@@ -176,6 +179,31 @@ __host__ __device__ inline size_t poa_lds_bytes(u32 pn, u32 ml, u32 lab32) {
   size_t const s_aln = size_t(12) * (pn + 2) + 8 * kSlowCap + size_t(4) * (pn + ml + 2);
   size_t const s_topo = size_t(10) * pn;
   return kStBytes + graph + (s_aln > s_topo ? s_aln : s_topo) + 16;
+}
+
+// What a workgroup's LDS block may take: the chip's 160 KB less the persistent kernel's static block (k_poa: sh_job).
+constexpr size_t kPoaLdsLimit = 160 * 1024 - 256;
+// Node capacity of a pass whose longest haplotype has max_len bases: a quarter more nodes than bases (at least 256), less
+// while that keeps two workgroups on a CU (80 KB each, down to 128 spare nodes) and less again to fit the block at all
+// (down to 32 spare nodes).
+inline u32 poa_node_capacity(u32 max_len, u32 lab32) {
+  u32 pn = max_len + std::max<u32>(256, max_len / 4);
+  pn = std::min<u32>((pn + 7) & ~7u, 65000);
+  while (!lab32 && poa_lds_bytes(pn, max_len, lab32) > 80 * 1024 && pn > max_len + 128) pn -= 8;
+  while (poa_lds_bytes(pn, max_len, lab32) > 159 * 1024 && pn > max_len + 32) pn -= 8;
+  return pn;
+}
+// The longest haplotype the stage takes: the graph (58 bytes of LDS per node, 66 with 32-bit label masks), the path buffer
+// (4 per base) and the state block of ONE window have to fit one workgroup's LDS.  A window with a longer haplotype is flagged
+// MA_W_LEN_OVERFLOW and left out (k_msa_maxima), as the build stage does with over-long reads; the batch goes on.
+inline u32 poa_max_hap_len(u32 lab32) {
+  auto const scan = [](u32 lab) {
+    u32 l = 4096;
+    while (l > 16 && poa_lds_bytes(poa_node_capacity(l, lab), l, lab) > kPoaLdsLimit) --l;
+    return l;
+  };
+  static u32 const common = scan(0u), wide = scan(1u);
+  return lab32 ? wide : common;
 }
 
 __device__ __forceinline__ GL poa_carve(u32 PN, u32 ML, u32 lab32) {
@@ -2121,8 +2149,33 @@ struct MsaArgs {
 
 // A batch with a component of more than 16 haplotypes runs in two passes (launch_msa): the common kernels over the windows
 // that fit 16-bit label masks, the LAB32 kernels -- 8 more bytes of LDS per node: one workgroup per CU -- over the few that do not.
+// longest haplotype of a window's components, and the most haplotypes of any of them
+__device__ __forceinline__ u32 window_longest_hap(ma_asm_out_t const& a, int w, u32 max_haps, u32 max_comps, u32* most_haps, u32* alignments) {
+  u32 ml = 0, mh = 0, al = 0;
+  u32 const nc = a.win_ncomp[w];
+  for (u32 c = 0; c < nc; ++c) {
+    size_t const ci = static_cast<size_t>(w) * max_comps + c;
+    u32 const nh = a.comp_nhaps[ci], h0 = a.comp_hap0[ci];
+    for (u32 h = 0; h < nh; ++h) ml = max(ml, a.hap_len[static_cast<size_t>(w) * max_haps + h0 + h]);
+    al += nh > 1 ? nh - 1 : 0;
+    mh = max(mh, nh);
+  }
+  *most_haps = mh;
+  *alignments = al;
+  return ml;
+}
+// A window takes the LAB32 kernels when one of its components holds more than 16 haplotypes (or every window does: all32),
+// and the kernels it takes decide how long its haplotypes may be.  k_msa_maxima flags by this, the passes skip by this.
+__device__ __forceinline__ bool window_too_long(u32 longest, u32 most_haps, u32 cap16, u32 cap32, u32 all32) {
+  return longest > ((all32 || most_haps > 16) ? cap32 : cap16);
+}
 __device__ __forceinline__ bool poa_window_skipped(MsaArgs const& A, int w) {
   if ((A.a.win_status[w] & MA_W_NO_HAPLOTYPE) || A.a.win_ncomp[w] == 0) return true;
+  if (A.ws.len_cap16) {  // (only in a batch that holds a flagged window) the windows k_msa_maxima left out: win_nvars = 0 is written
+    u32 mh, al;
+    u32 const ml = window_longest_hap(A.a, w, static_cast<u32>(A.prm.max_haps), static_cast<u32>(A.prm.max_comps), &mh, &al);
+    if (window_too_long(ml, mh, A.ws.len_cap16, A.ws.len_cap32, A.ws.len_all32)) return true;
+  }
   if (A.ws.pass == 0) return false;
   bool wide = false;
   u32 const nc = A.a.win_ncomp[w];
@@ -2920,6 +2973,15 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
             A.o.var_hap_allele[vi * MH + hx] = 0;
             A.o.var_hap_start[vi * MH + hx] = 0;
           }
+          // The ALT slots this variant does not fill read 0, whatever the buffer held: the host route delivers a used variant's
+          // whole row of max_alts slots from the lane's own device buffers, which nobody clears -- two runs of one batch
+          // differed there (tests/test_gpu_general_deferral.py compares whole arrays)
+          for (int ax = static_cast<int>(ngrp); ax < MA; ++ax) {
+            A.o.alt_off[vi * MA + ax] = 0;
+            A.o.alt_len[vi * MA + ax] = 0;
+            A.o.alt_type[vi * MA + ax] = 0;
+            A.o.alt_length[vi * MA + ax] = 0;
+          }
           u32(&rank_of_grp)[kMaxSeq] = ST.xa_rank_of_grp;
           for (u32 ai = 0; ai < ngrp; ++ai) {
             u32 const gi = ordg[ai];
@@ -3350,21 +3412,27 @@ extern "C" void ma_debug_prof(unsigned long long* out, int reset) {
 #endif
 
 // longest haplotype that is aligned and the most alignments of any window (what launch_msa sizes the graph and its rounds by)
-__global__ __launch_bounds__(256) void k_msa_maxima(ma_asm_out_t a, int n, u32 max_haps, u32 max_comps, u32* out) {
+// A window with a haplotype longer than one LDS block holds (cap16: the common kernels, cap32: the LAB32 kernels, which a
+// window with a component of more than 16 haplotypes takes, or every window when `all32`) is flagged MA_W_LEN_OVERFLOW here,
+// gets win_nvars = 0 and counts for nothing: the passes are sized from the others and skip it (poa_window_skipped).
+__global__ __launch_bounds__(256) void k_msa_maxima(ma_asm_out_t a, int n, u32 max_haps, u32 max_comps, u32 cap16, u32 cap32, u32 all32,
+                                                    u32* win_nvars, u32* out) {
   int const w = blockIdx.x * 256 + threadIdx.x;
   // out[0] / out[1]: over all windows; out[2]: most haplotypes of any component; out[3]: longest haplotype of a window
-  // that holds such a wide component (sizes the LAB32 pass)
+  // that holds such a wide component (sizes the LAB32 pass); out[4]: windows flagged here
   u32 ml = 0, al = 0, mh = 0, mlw = 0;
+  bool too_long = false;
   if (w < n && !(a.win_status[w] & MA_W_NO_HAPLOTYPE)) {
-    for (u32 c = 0; c < a.win_ncomp[w]; ++c) {
-      size_t const ci = static_cast<size_t>(w) * max_comps + c;
-      u32 const nh = a.comp_nhaps[ci], h0 = a.comp_hap0[ci];
-      for (u32 h = 0; h < nh; ++h) ml = max(ml, a.hap_len[static_cast<size_t>(w) * max_haps + h0 + h]);
-      al += nh > 1 ? nh - 1 : 0;
-      mh = max(mh, nh);
+    ml = window_longest_hap(a, w, max_haps, max_comps, &mh, &al);
+    if (window_too_long(ml, mh, cap16, cap32, all32)) {
+      too_long = true;
+      a.win_status[w] |= MA_W_LEN_OVERFLOW;
+      win_nvars[w] = 0;
+      ml = al = mh = 0;
     }
     if (mh > 16) mlw = ml;
   }
+  if (too_long) atomicAdd(&out[4], 1u);
   for (int off = 32; off > 0; off >>= 1) {
     ml = max(ml, __shfl_xor(ml, off));
     al = max(al, __shfl_xor(al, off));
@@ -3411,7 +3479,7 @@ int launch_msa(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var
   return rc;
 }
 static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o, u32 max_len, u32 rounds,
-                           u32 lab32, u32 pass);
+                           u32 lab32, u32 pass, const u32 (&len_caps)[3]);
 static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o) {
   int const n = b.n_windows;
   if (n == 0) return MA_OK;
@@ -3425,45 +3493,54 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
     return MA_ERR_PARAM;
   }
   // longest haplotype of the batch decides the DP width and the LDS graph capacity (one small D2H)
-  u32 got[4] = {0, 0, 0, 0};
+  u32 got[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  u32 const cap16 = poa_max_hap_len(0u), cap32 = poa_max_hap_len(1u);
+  if (ctx->poa_all32 < 0) {  // once per context: the switch, and the bound under MA_VERBOSE
+    ctx->poa_all32 = getenv("MA_POA_FORCE_LAB32") ? 1 : 0;  // tests: every window through LAB32
+    if (getenv("MA_VERBOSE"))
+      fprintf(stderr, "[microasm] msa: longest haplotype one LDS block holds: %u bases (%u in the LAB32 kernels)\n", cap16, cap32);
+  }
+  bool const all32 = ctx->poa_all32 == 1;
   {
     // (on the device: the five arrays used to come back whole -- 0.3 MB per lane into pageable memory, staged copies and a
     //  host loop in front of every lane's POA rounds -- for a few numbers)
     MA_HIP(ctx, ctx->ws_build.reserve(4096));
     u32* mx = static_cast<u32*>(ctx->ws_build.p);
-    MA_HIP(ctx, hipMemsetAsync(mx, 0, 16, ctx->stream));
+    MA_HIP(ctx, hipMemsetAsync(mx, 0, 32, ctx->stream));
     hipLaunchKernelGGL(k_msa_maxima, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a, n, static_cast<u32>(P.max_haps),
-                       static_cast<u32>(P.max_comps), mx);
-    MA_HIP(ctx, hipMemcpyAsync(got, mx, 16, hipMemcpyDeviceToHost, ctx->stream));
+                       static_cast<u32>(P.max_comps), cap16, cap32, all32 ? 1u : 0u, o.win_nvars, mx);
+    MA_HIP(ctx, hipMemcpyAsync(got, mx, 32, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));
   }
   u32 const rounds = std::max<u32>(1u, got[1] + 1u);  // split mode: 1 + the most alignments of any window
   bool const any_wide = got[2] > 16;
-  if (getenv("MA_POA_FORCE_LAB32")) return launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u);  // tests: every window through LAB32
+  bool const flagged = got[4] != 0;  // windows left out for their length: the passes have to step over them
+  u32 const caps[3] = {flagged ? cap16 : 0u, cap32, all32 ? 1u : 0u};
+  if (all32) return launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u, caps);
   // The reference has no cap on the haplotypes of a component (cbdg/graph.cpp:846-924, caller/msa_builder.cpp:29-42); the
   // engine's is the caller's max_haps <= 32.  Components of up to 16 haplotypes take the common kernels (16-bit label masks,
   // two workgroups per CU); a window with a wider component takes the LAB32 kernels in a pass of its own.
-  MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 0u, any_wide ? 1u : 0u));
-  if (any_wide) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, std::max(got[3], 16u), rounds, 1u, 2u));
+  MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 0u, any_wide ? 1u : 0u, caps));
+  if (any_wide) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, std::max(got[3], 16u), rounds, 1u, 2u, caps));
   return MA_OK;
 }
 static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o, u32 max_len, u32 rounds,
-                           u32 const lab32, u32 const pass) {
+                           u32 const lab32, u32 const pass, const u32 (&len_caps)[3]) {
   int const n = b.n_windows;
   ma_params_t const& P = ctx->prm;
   PoaWs ws{};
   MA_TRY_RC(ma_dev_stats(ctx, &ws.dstats));
   ws.lab32 = lab32;
   ws.pass = pass;
+  ws.len_cap16 = len_caps[0];
+  ws.len_cap32 = len_caps[1];
+  ws.len_all32 = len_caps[2];
   max_len = std::max<u32>(max_len, 16);
   ws.max_l = max_len;
-  u32 pn = max_len + std::max<u32>(256, max_len / 4);
-  pn = std::min<u32>((pn + 7) & ~7u, 65000);
   // two workgroups per CU when the graph fits in 80 KB of LDS, one otherwise
-  while (!lab32 && poa_lds_bytes(pn, max_len, lab32) > 80 * 1024 && pn > max_len + 128) pn -= 8;
-  while (poa_lds_bytes(pn, max_len, lab32) > 159 * 1024 && pn > max_len + 32) pn -= 8;
+  u32 const pn = poa_node_capacity(max_len, lab32);
   size_t const lds = poa_lds_bytes(pn, max_len, lab32);
-  if (lds > 160 * 1024) {
+  if (lds > kPoaLdsLimit) {  // (not reached: k_msa_maxima has left the windows out that are longer than poa_max_hap_len)
     ma_set_err(ctx, "ma_msa_batch: haplotypes too long for the LDS-resident POA graph");
     return MA_ERR_PARAM;
   }

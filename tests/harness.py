@@ -346,6 +346,32 @@ def handmade_genotype_case(p, windows):
     return asm, var
 
 
+def handmade_poa_case(p, windows):
+    """handmade_genotype_case's sibling for the POA stage: assembly buffers only, the input of Engine.msa / OracleEngine.msa.
+    windows = [[(haps, anchor), ...], ...]: per window its components, each a list of haplotype byte strings (the first one is
+    the REF haplotype) and its comp_anchor; the haplotype slots are numbered through the components in order."""
+    n = len(windows)
+    asm = capi.alloc_host(capi.asm_out_spec(p, n))
+    MC, MH, ML = p.max_comps, p.max_haps, p.max_hap_len
+    for w, comps in enumerate(windows):
+        assert len(comps) <= MC and sum(len(haps) for haps, _ in comps) <= MH
+        asm["win_ncomp"][w] = len(comps)
+        asm["win_k"][w] = 25
+        hap0 = 0
+        for c, (haps, anchor) in enumerate(comps):
+            ci = w * MC + c
+            asm["comp_hap0"][ci] = hap0
+            asm["comp_nhaps"][ci] = len(haps)
+            asm["comp_anchor"][ci] = anchor
+            for h, seq in enumerate(haps):
+                hi = w * MH + hap0 + h
+                assert 0 < len(seq) <= ML
+                asm["hap_len"][hi] = len(seq)
+                asm["hap_bases"][hi * ML:hi * ML + len(seq)] = np.frombuffer(bytes(seq), np.uint8)
+            hap0 += len(haps)
+    return asm
+
+
 class DeviceArena:
     """hipMalloc / hipMemcpy through ctypes on the HIP runtime the product library is using (no torch import: the
     first import of torch on a cold box takes minutes).  Test infrastructure for the MA_MEM_DEVICE entry points."""

@@ -6,7 +6,7 @@ its own (poa.hip: launch_msa).  Checked against the oracle, whose POA has no suc
 import numpy as np
 import pytest
 
-from harness import OracleEngine, compare_asm, compare_geno_calls, compare_vars
+from harness import OracleEngine, compare_asm, compare_geno_calls, compare_vars, handmade_poa_case
 from lancet2_amd import capi, synth
 from pin_cases import rand_dna
 
@@ -14,24 +14,16 @@ pytestmark = pytest.mark.gpu
 
 
 def _hand_asm(params, comps_per_window, rng):
-    """assembly buffers written by hand: window w holds the components comps_per_window[w] = [n_haplotypes, ...]; every
-    component is a random ~950-base REF haplotype + ALT haplotypes that each carry their own subset of a pool of planted
-    variants (SNVs, a 3-base deletion, a 5-base insertion, a 24-base deletion: one ALT allele per site)"""
-    n = len(comps_per_window)
-    asm = capi.alloc_host(capi.asm_out_spec(params, n))
-    MC, MH, ML = params.max_comps, params.max_haps, params.max_hap_len
-    for w, comps in enumerate(comps_per_window):
-        asm["win_ncomp"][w] = len(comps)
-        asm["win_k"][w] = 25
-        h0 = 0
+    """assembly buffers written by hand (harness.handmade_poa_case): window w holds the components comps_per_window[w] =
+    [n_haplotypes, ...]; every component is a random ~950-base REF haplotype + ALT haplotypes that each carry their own subset
+    of a pool of planted variants (SNVs, a 3-base deletion, a 5-base insertion, a 24-base deletion: one ALT allele per site)"""
+    windows = []
+    for comps in comps_per_window:
+        win = []
         for c, nh in enumerate(comps):
-            ci = w * MC + c
             ref = rand_dna(rng, int(rng.integers(900, 1001)))
             sites = list(range(40, len(ref) - 60, 55))
             kinds = ["snv", "del3", "ins5", "snv", "del24", "snv"]
-            asm["comp_hap0"][ci] = h0
-            asm["comp_nhaps"][ci] = nh
-            asm["comp_anchor"][ci] = 17 + c
             seen = {ref}
             haps = [ref]
             while len(haps) < nh:
@@ -51,12 +43,9 @@ def _hand_asm(params, comps_per_window, rng):
                 if hb not in seen:
                     seen.add(hb)
                     haps.append(hb)
-            for h, seq in enumerate(haps):
-                hi = w * MH + h0 + h
-                asm["hap_len"][hi] = len(seq)
-                asm["hap_bases"][hi * ML:hi * ML + len(seq)] = np.frombuffer(seq, np.uint8)
-            h0 += nh
-    return asm
+            win.append((haps, 17 + c))
+        windows.append(win)
+    return handmade_poa_case(params, windows)
 
 
 @pytest.mark.parametrize("force_lab32", [False, True])
