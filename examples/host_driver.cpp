@@ -19,7 +19,7 @@
 //
 //   g++ -std=c++17 -O2 examples/host_driver.cpp -Iinclude -Llancet2_amd -lmicroasm -Wl,-rpath,$PWD/lancet2_amd
 //       -Wl,--allow-shlib-undefined -lpthread -o host_driver
-//   ./host_driver --windows 256 --batch 64 --feeders 2 [--devices 1] [--germline] [--dump DIR] [--out FILE]
+//   ./host_driver --windows 256 --batch 64 --feeders 2 [--devices 1] [--germline] [--poa-retry] [--dump DIR] [--out FILE]
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -257,7 +257,7 @@ struct BatchResult {
 }  // namespace
 
 int main(int argc, char** argv) {
-  int n_windows = 128, batch = 64, feeders = 1, devices = 1, germline = 0;
+  int n_windows = 128, batch = 64, feeders = 1, devices = 1, germline = 0, poa_retry = 0;
   std::string dump, out_path;
   for (int i = 1; i < argc; ++i) {
     std::string const a = argv[i];
@@ -267,6 +267,7 @@ int main(int argc, char** argv) {
     else if (a == "--feeders") feeders = std::atoi(next());
     else if (a == "--devices") devices = std::atoi(next());
     else if (a == "--germline") germline = 1;
+    else if (a == "--poa-retry") poa_retry = 1;  // windows whose POA graph overflowed get the engine's second pass (default: off)
     else if (a == "--dump") dump = next();
     else if (a == "--out") out_path = next();
   }
@@ -296,6 +297,7 @@ int main(int argc, char** argv) {
       return 3;
     }
     ma_set_streams(ctx[static_cast<size_t>(g)], 1);
+    ma_set_poa_retry(ctx[static_cast<size_t>(g)], poa_retry);
   }
   std::vector<BatchResult> results(static_cast<size_t>(n_batches));
   std::mutex mu;
@@ -360,6 +362,7 @@ int main(int argc, char** argv) {
     std::map<int, std::vector<std::string>> redo;  // window -> its records from the larger buffers
     std::set<int> redone;                            // windows whose re-submission succeeded (possibly with no record)
     if (ma_create(&big, 0, MA_MEM_HOST, &c2) == MA_OK) {
+      ma_set_poa_retry(c2, poa_retry);  // (larger caps do not cure a flag the POA graph raised: this does)
       for (int w : flagged) {
         FlatBatch fb;
         Outputs o2;

@@ -213,7 +213,7 @@ int main(int argc, char** argv) {
   ReadCollector::Params rp;
   ma_params_t prm;
   ma_default_params(&prm);
-  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false;
+  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false, poa_retry = false;
   int batch_windows = 512;
   int extract_threads = static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
   for (int i = 1; i < argc; ++i) {
@@ -244,6 +244,7 @@ int main(int argc, char** argv) {
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
     else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
+    else if (a == "--poa-retry") poa_retry = true;  // ma_set_poa_retry: a second POA pass over the windows whose graph overflowed
     else if (a == "--extract-only") extract_only = true;  // stage 1 alone (with --dump): no device needed
     else { std::fprintf(stderr, "pipeline_driver: unknown option %s\n", a.c_str()); return 2; }
   }
@@ -255,7 +256,9 @@ int main(int argc, char** argv) {
                          "                  as it is.  Not with --collect-reads / --extract-pairs\n"
                          "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
                          "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
-                         "                  all 24 FORMAT values.  Without it those six are \".\"\n");
+                         "                  all 24 FORMAT values.  Without it those six are \".\"\n"
+                         "  --poa-retry     windows whose POA graph ran out of nodes or of per-node edge slots (MA_W_VAR_OVERFLOW that larger\n"
+                         "                  caps do not cure) are re-run by the engine with a larger graph.  Default: off\n");
     return 2;
   }
   if (packed_reads && (collect_reads || rp.extract_pairs)) {
@@ -307,6 +310,7 @@ int main(int argc, char** argv) {
                  crc == MA_ERR_NO_DEVICE ? " (no HIP device: the engine has no CPU fallback)" : "");
     return 3;
   }
+  if (ctx && poa_retry) ma_set_poa_retry(ctx, 1);
 
   Channel<Job> to_engine(3), to_flush(3);
   // batches whose records are flushed go back to the extract stage with their arrays' memory (a fresh batch is 300 MB of

@@ -396,6 +396,18 @@ int ma_last_kernel_times(ma_ctx_t* ctx, const char** names, float* ms, int cap);
  * The caller's stream (ma_set_stream) still orders the call as a whole. */
 int ma_set_streams(ma_ctx_t* ctx, int n);
 
+/* 0 (default): the POA stage as it is.  1: windows whose POA graph ran out of nodes or of per-node edge / aligned-node
+ * slots are re-run inside the call -- from their first component -- by a second pass with a larger graph; only what that
+ * pass cannot hold either stays MA_W_VAR_OVERFLOW.  Applies to ma_msa_batch and every chained call, on every lane and route.
+ * Results of windows that were not flagged never depend on it.  Any other value of `on`: MA_ERR_ARG.
+ * (MA_W_VAR_OVERFLOW from an output cap -- max_vars, max_alts, max_allele_bytes -- is cured by larger caps, not by this.) */
+int ma_set_poa_retry(ma_ctx_t* ctx, int on);
+/* Of the last call that ran the POA stage, summed over its lanes:
+ *   out[0] windows marked for the edge width   out[1] marked for the node capacity only
+ *   out[2] windows the retry passes called     out[3] windows left MA_W_VAR_OVERFLOW by them
+ * All zero while the setting is off.  Returns the number of entries written. */
+int ma_last_poa_retry(ma_ctx_t* ctx, unsigned long long* out, int cap);
+
 /* Work counters accumulated over the same region as ma_last_kernel_times (reset by ma_timing_control):
  *   out[0] read x haplotype pairs seen by ma_genotype_batch      out[1] pairs that needed the DP
  *   out[2] windows passed to ma_assemble_batch                   out[3] k attempts x windows assembled

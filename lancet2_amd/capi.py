@@ -116,6 +116,10 @@ class CxOut(C.Structure):
 
 # ma_process_cx_batch(ctx, batch, packed, meta, gate, asm, var, geno, fmt, fmeta, double gc_frac, cx)
 PROCESS_CX_ARGTYPES = [C.c_void_p] * 10 + [C.c_double, C.c_void_p]
+# ma_set_poa_retry(ctx, int on) / ma_last_poa_retry(ctx, unsigned long long* out, int cap)
+SET_POA_RETRY_ARGTYPES = [C.c_void_p, C.c_int]
+LAST_POA_RETRY_ARGTYPES = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+POA_RETRY_KEYS = ("marked_width", "marked_capacity", "called", "left_flagged")
 
 
 BATCH_DTYPES = dict(ref_bases=np.uint8, ref_off=np.uint32, read_win_off=np.uint32,

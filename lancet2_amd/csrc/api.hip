@@ -376,6 +376,8 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk,
     if (!ch->accumulate) ch->timers_used = 0;
     ch->hbm_share = ctx->hbm_share / lanes;
     ch->co_lanes = lanes;
+    ch->poa_retry = ctx->poa_retry;
+    for (auto& c : ch->poa_retry_counts) c = 0;
   }
   if (!ctx->dev_pool) ctx->dev_pool = new DevLanePool();
   static_cast<DevLanePool*>(ctx->dev_pool)->run(lanes, [&](int k) {
@@ -387,6 +389,10 @@ int process_in_lanes(ma_ctx* ctx, int lanes, const DBatch& d, const DPacked* pk,
       return rc[k];
     }
     MA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lanes[k]->lane_done, 0));
+  }
+  for (int x = 0; x < 4; ++x) {  // ma_last_poa_retry: the call's counts are the lanes' sum
+    ctx->poa_retry_counts[x] = 0;
+    for (int k = 0; k < lanes; ++k) ctx->poa_retry_counts[x] += ctx->lanes[k]->poa_retry_counts[x];
   }
   return MA_OK;
 }
@@ -659,6 +665,7 @@ struct LaneResult {
   size_t aux_off = 0, packed_off = 0, packed_bytes = 0;
   std::vector<std::pair<const char*, float>> times;  // the lane's kernel timers of this job, resolved
   unsigned long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long poa_retry[4] = {0, 0, 0, 0};  // the lane's counts of ma_last_poa_retry
 };
 struct UploadTask {  // the inputs of one prefetched batch, all lanes: carried out by the context's uploader thread
   std::vector<CopyOp> ops;           // lane after lane
@@ -686,6 +693,7 @@ struct HostJob {
   ma_params_t prm{};
   bool timing = false, accumulate = false, collect = false;
   double hbm_share = 1.0;
+  int poa_retry = 0;                  // ma_set_poa_retry, as it stood when the job was queued
   u32 mask = 0;                       // seg_table entries to compute and pack
   double gc_frac = 0.0;               // the annotation's GC fraction (read when the mask holds the annotation's entries)
   std::shared_ptr<UploadTask> upload; // the upload ma_prefetch_batch started (null: every lane uploads its slice)
@@ -742,6 +750,8 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
   ch->accumulate = job.accumulate;
   ch->collect = job.collect;
   ch->hbm_share = job.hbm_share;
+  ch->poa_retry = job.poa_retry;
+  for (auto& c : ch->poa_retry_counts) c = 0;
   ch->co_lanes = static_cast<int>(job.wb.size()) - 1;
   ch->timers_used = 0;
   for (auto& s : ch->stats) s = 0;
@@ -891,6 +901,7 @@ int lane_compute(ma_ctx* ch, HostJob& job, int k) {
     R.stats[x] = ch->stats[x];
     ch->stats[x] = 0;
   }
+  for (int x = 0; x < 4; ++x) R.poa_retry[x] = ch->poa_retry_counts[x];
   if (verbose)
     fprintf(stderr, "[microasm] t=%.1f host lane [%d, %d): enqueue-upload %.2f gate %.2f assemble %.2f msa %.2f genotype %.2f pack %.2f "
             "download %.2f ms; %.1f MB in, %.2f MB packed out\n", wall_ms(), w0, w1, t_up, t_gate - t_up, t_asm - t_gate,
@@ -1111,6 +1122,7 @@ std::shared_ptr<HostJob> submit_host(ma_ctx* ctx, int lanes, const ma_batch_t* b
   job->accumulate = ctx->accumulate;
   job->collect = ctx->collect;
   job->hbm_share = ctx->hbm_share / lanes;
+  job->poa_retry = ctx->poa_retry;
   job->mask = mask;
   job->gc_frac = gc_frac;
   job->upload = upload;
@@ -1183,7 +1195,8 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
   }
   std::shared_ptr<HostJob> job = ha->jobs[set];
   if (job && (job->mask != mask || std::memcmp(&job->gc_frac, &gc_frac, sizeof(double)) != 0 || taps || std::memcmp(&job->prm, &ctx->prm, sizeof(ma_params_t)) != 0 ||
-              job->timing != ctx->timing || job->accumulate != ctx->accumulate || job->collect != ctx->collect)) {
+              job->timing != ctx->timing || job->accumulate != ctx->accumulate || job->collect != ctx->collect ||
+              job->poa_retry != ctx->poa_retry)) {
     job->wait_all();  // queued ahead under other assumptions than this call's: computed again below, from the staged inputs
     job.reset();
   }
@@ -1196,8 +1209,10 @@ int process_host(ma_ctx* ctx, int lanes, const ma_batch_t* b, const ma_packed_re
   job->wait_all();
   if (!ctx->accumulate) ha->times.clear();
   int rc = MA_OK;
+  for (auto& c : ctx->poa_retry_counts) c = 0;
   for (int k = 0; k < lanes; ++k) {
     LaneResult const& R = job->res[k];
+    for (int x = 0; x < 4; ++x) ctx->poa_retry_counts[x] += R.poa_retry[x];
     if (R.rc != MA_OK && rc == MA_OK) {
       ma_set_err(ctx, "lane " + std::to_string(k) + ": " + R.err);
       rc = R.rc;
@@ -1287,6 +1302,7 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->pack_aux.release();
   ctx->ws_unpack.release();
   ctx->ws_sort.release();
+  ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
     pp = nullptr;
@@ -1360,6 +1376,19 @@ int ma_set_streams(ma_ctx_t* ctx, int n) {
   if (!ctx || n < 0 || n > 8) return MA_ERR_ARG;
   ctx->n_lanes = n;
   return MA_OK;
+}
+
+int ma_set_poa_retry(ma_ctx_t* ctx, int on) {
+  if (!ctx || (on != 0 && on != 1)) return MA_ERR_ARG;
+  ctx->poa_retry = on;  // (a job queued ahead under the other setting is dropped by the call that finds it: process_host)
+  return MA_OK;
+}
+
+int ma_last_poa_retry(ma_ctx_t* ctx, unsigned long long* out, int cap) {
+  if (!ctx || !out) return MA_ERR_ARG;
+  int n = 0;
+  for (; n < cap && n < 4; ++n) out[n] = ctx->poa_retry_counts[n];
+  return n;
 }
 
 int ma_last_stats(ma_ctx_t* ctx, unsigned long long* out, int cap) {

@@ -117,6 +117,12 @@ struct ma_ctx {
   bool hi_failed = false;
   int poa_all32 = -1;       // MA_POA_FORCE_LAB32, read at the context's first POA call (-1: not yet)
   double hbm_share = 1.0;   // fraction of the device this context plans its workspaces for
+  // ma_set_poa_retry: the setting (a lane takes its parent's per call, like hbm_share), the per-window cause marks of a POA call
+  // -- a buffer of their own: the stage's arena ws_build is re-reserved by every pass and may move -- with the 64-byte counter
+  // block of k_poa_retry_select in front, and the counts ma_last_poa_retry reports (a parent's: the sum over the call's lanes)
+  int poa_retry = 0;
+  ma::DevBuf poa_cause;
+  unsigned long long poa_retry_counts[4] = {0, 0, 0, 0};
   hipEvent_t sync_ev = nullptr;  // blocking-sync event: host threads sleep instead of spinning while the stream drains
   // host route (MA_MEM_HOST) of ma_process_batch, per lane: packed result records (pack.hip) and their pinned landing area
   ma::DevBuf pack_aux;

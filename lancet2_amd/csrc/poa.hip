@@ -46,7 +46,8 @@ namespace ma {
 
 namespace {
 
-constexpr int kPE = 4;        // in / out edges and aligned nodes kept per POA node
+// In / out edges and aligned nodes kept per POA node: a template constant of the kernels, PE = 4 (every first pass, the
+// retry's capacity pass) or 8 (the retry's width pass: ma_set_poa_retry).  The graph views carry it as G::pe.
 constexpr int kT = 256;       // threads per window
 constexpr u32 kSlowCap = 256; // rows with a cached predecessor-row list
 constexpr u32 kMaxSeq = 32;   // haplotypes per component: the per-edge label masks are 16 bit (common kernel) or 32 bit (LAB32)
@@ -61,6 +62,26 @@ constexpr u32 RI_SLOWTAB = 1u << 12;  // predecessor rows cached in slowpred[inf
 constexpr u32 RI_STORE = 1u << 13;    // a later row reads this row back from HBM
 constexpr u32 RI_LEAN = 1u << 14;     // band tiers: the row takes the straight-line path of poa_fill_lean (see band_flags)
 constexpr u32 RI_SLIDE = 1u << 15;    // ... and its window sits one lane to the right of the previous row's
+// A row's descriptor holds its number of predecessors in bits [10:8]: 0 .. 4 with four slots.  With eight slots the count
+// reaches 8, whose fourth bit goes to bit 24 (a row that is not FAST keeps [23:16] for its slowpred index and nothing above).
+template <int PE>
+__device__ __forceinline__ u32 ri_np(u32 info) {
+  if constexpr (PE <= 4) return (info >> 8) & 7u;
+  else return ((info >> 8) & 7u) | ((info >> 21) & 8u);
+}
+template <int PE>
+__device__ __forceinline__ u32 ri_np_bits(u32 np) {
+  if constexpr (PE <= 4) return np << 8;
+  else return ((np & 7u) << 8) | ((np & 8u) << 21);
+}
+// Bits of a predecessor index in a decision code (plane B holds two of them: 4 or 6 of its byte's bits)
+template <int PE>
+constexpr u32 kXB = PE <= 4 ? 2u : 3u;
+// What sets WgState::overflow, kept apart so that a flagged window knows what a retry would have to lift
+constexpr u32 kOvNodes = 1u;  // the graph ran out of nodes (or of something sized by the node capacity)
+constexpr u32 kOvSlots = 2u;  // a node ran out of edge or aligned-node slots
+constexpr u32 kOvOther = 4u;  // a component with more haplotypes than the kernel's label masks hold: no retry lifts that
+constexpr u32 kCauseLeft = 0x80u;  // PoaWs::cause: marked, but longer than the retry pass it needs can hold: stays flagged
 
 struct PoaWs {
   u32 pn;            // node capacity (LDS)
@@ -78,6 +99,10 @@ struct PoaWs {
   u32 lean;          // band tiers run poa_fill_lean (default) / poa_fill_band (MA_POA_LEAN=0; same codes, tested)
   u32 lab32;         // this pass runs the kernels with 32-bit label masks (components of 17 .. 32 haplotypes)
   u32 pass;          // 0: every window; 1: only windows whose components all hold <= 16 haplotypes; 2: only the others
+                     // retry passes (ma_set_poa_retry), over the windows `cause` marks: 3 / 4: marked for the slot width,
+                     // <= 16 / more haplotypes; 5 / 6: marked for the node capacity only, <= 16 / more haplotypes
+  u8* cause;         // [window] why the POA graph overflowed (kOvNodes | kOvSlots; kCauseLeft: the retry does not take it);
+                     // null unless the context's retry setting is on
   // The batch holds windows that k_msa_maxima flagged MA_W_LEN_OVERFLOW (else len_cap16 = 0): its two caps and `all32`, so
   // that every pass steps over exactly the windows it flagged (window_too_long: one predicate for both)
   u32 len_cap16, len_cap32, len_all32;
@@ -142,7 +167,9 @@ struct WgState {
 #define ST (*reinterpret_cast<WgState*>(ma_lds))
 constexpr u32 kStBytes = (sizeof(WgState) + 15u) & ~15u;
 
-struct GL {  // LDS layout of one window's POA graph + scratch
+template <int PE_>
+struct GLT {  // LDS layout of one window's POA graph + scratch
+  static constexpr int pe = PE_;  // edge / aligned-node slots per node
   u32 pn;
   LdsArr<u8> nchar, nin, nout, nal;
   LdsArr<u16> in_tail, out_head, al, rank2node, node2rank;
@@ -174,10 +201,11 @@ struct GL {  // LDS layout of one window's POA graph + scratch
   __device__ __forceinline__ u32 uword(const void* p) const { return *static_cast<const u32*>(p); }
 };
 
-__host__ __device__ inline size_t poa_lds_bytes(u32 pn, u32 ml, u32 lab32) {
-  size_t const graph = size_t(lab32 ? 50 : 42) * pn;
-  size_t const s_aln = size_t(12) * (pn + 2) + 8 * kSlowCap + size_t(4) * (pn + ml + 2);
-  size_t const s_topo = size_t(10) * pn;
+// pe = 4: 42 bytes of graph per node (50 with 32-bit label masks), pe = 8: 74 (90)
+__host__ __device__ inline size_t poa_lds_bytes(u32 pn, u32 ml, u32 lab32, u32 pe) {
+  size_t const graph = size_t(10 + pe * (lab32 ? 10 : 8)) * pn;
+  size_t const s_aln = size_t(12) * (pn + 2) + 2 * pe * kSlowCap + size_t(4) * (pn + ml + 2);
+  size_t const s_topo = size_t(2 * pe + 2) * pn;
   return kStBytes + graph + (s_aln > s_topo ? s_aln : s_topo) + 16;
 }
 
@@ -189,9 +217,24 @@ constexpr size_t kPoaLdsLimit = 160 * 1024 - 256;
 inline u32 poa_node_capacity(u32 max_len, u32 lab32) {
   u32 pn = max_len + std::max<u32>(256, max_len / 4);
   pn = std::min<u32>((pn + 7) & ~7u, 65000);
-  while (!lab32 && poa_lds_bytes(pn, max_len, lab32) > 80 * 1024 && pn > max_len + 128) pn -= 8;
-  while (poa_lds_bytes(pn, max_len, lab32) > 159 * 1024 && pn > max_len + 32) pn -= 8;
+  while (!lab32 && poa_lds_bytes(pn, max_len, lab32, 4) > 80 * 1024 && pn > max_len + 128) pn -= 8;
+  while (poa_lds_bytes(pn, max_len, lab32, 4) > 159 * 1024 && pn > max_len + 32) pn -= 8;
   return pn;
+}
+// Node capacity of a retry pass (ma_set_poa_retry): the most nodes, a multiple of 8, one workgroup's LDS block holds beside
+// a haplotype of max_len bases with `pe` slots per node; 0 when not even max_len + 32 nodes fit.
+inline u32 poa_node_capacity_max(u32 max_len, u32 lab32, u32 pe) {
+  u32 const floor_pn = (max_len + 32 + 7) & ~7u;
+  if (poa_lds_bytes(floor_pn, max_len, lab32, pe) > kPoaLdsLimit) return 0;
+  u32 pn = floor_pn;
+  while (pn + 8 <= 65000 && poa_lds_bytes(pn + 8, max_len, lab32, pe) <= kPoaLdsLimit) pn += 8;
+  return pn;
+}
+// The longest haplotype a retry pass takes: the one that leaves 32 spare nodes
+inline u32 poa_retry_max_hap_len(u32 lab32, u32 pe) {
+  u32 l = 4096;
+  while (l > 16 && poa_node_capacity_max(l, lab32, pe) == 0) --l;
+  return l;
 }
 // The longest haplotype the stage takes: the graph (58 bytes of LDS per node, 66 with 32-bit label masks), the path buffer
 // (4 per base) and the state block of ONE window have to fit one workgroup's LDS.  A window with a longer haplotype is flagged
@@ -199,15 +242,16 @@ inline u32 poa_node_capacity(u32 max_len, u32 lab32) {
 inline u32 poa_max_hap_len(u32 lab32) {
   auto const scan = [](u32 lab) {
     u32 l = 4096;
-    while (l > 16 && poa_lds_bytes(poa_node_capacity(l, lab), l, lab) > kPoaLdsLimit) --l;
+    while (l > 16 && poa_lds_bytes(poa_node_capacity(l, lab), l, lab, 4) > kPoaLdsLimit) --l;
     return l;
   };
   static u32 const common = scan(0u), wide = scan(1u);
   return lab32 ? wide : common;
 }
 
-__device__ __forceinline__ GL poa_carve(u32 PN, u32 ML, u32 lab32) {
-  GL g;
+template <int PE>
+__device__ __forceinline__ GLT<PE> poa_carve(u32 PN, u32 ML, u32 lab32) {
+  GLT<PE> g;
   g.pn = PN;
   g.lab32 = lab32;
   u32 o = kStBytes;
@@ -217,10 +261,10 @@ __device__ __forceinline__ GL poa_carve(u32 PN, u32 ML, u32 lab32) {
   g.nal.off = o + 3 * PN;
   o += 4 * PN;
   g.in_tail.off = o;
-  g.out_head.off = o + 8 * PN;
-  g.out_lab_off = o + 16 * PN;
-  g.al.off = o + (lab32 ? 32 : 24) * PN;
-  o += (lab32 ? 40 : 32) * PN;
+  g.out_head.off = o + 2 * PE * PN;
+  g.out_lab_off = o + 4 * PE * PN;
+  g.al.off = o + (lab32 ? 8 : 6) * PE * PN;
+  o += (lab32 ? 10 : 8) * PE * PN;
   g.rank2node.off = o;
   g.node2rank.off = o + 2 * PN;
   g.npos.off = o + 4 * PN;
@@ -232,15 +276,15 @@ __device__ __forceinline__ GL poa_carve(u32 PN, u32 ML, u32 lab32) {
   g.runhead.off = S + 8 * (PN + 2);
   g.rowj0.off = S + 10 * (PN + 2);
   g.slowpred.off = S + 12 * (PN + 2);
-  g.aln.off = S + 12 * (PN + 2) + 8 * kSlowCap;
+  g.aln.off = S + 12 * (PN + 2) + 2 * PE * kSlowCap;
   g.aln_cap = PN + ML + 2;
   g.cnode.off = S;
   g.cpos.off = S + 2 * (ML + 2);
   g.ccur.off = S + 4 * (ML + 2);
   g.stack.off = S;
-  g.stack_cap = 4 * PN;
-  g.marks.off = S + 8 * PN;
-  g.ignored.off = S + 9 * PN;
+  g.stack_cap = PE * PN;
+  g.marks.off = S + 2 * PE * PN;
+  g.ignored.off = S + (2 * PE + 1) * PN;
   return g;
 }
 
@@ -248,7 +292,8 @@ __device__ __forceinline__ GL poa_carve(u32 PN, u32 ML, u32 lab32) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- serial graph primitives (thread 0): spoa::Graph ----
-__device__ __forceinline__ i32 pg_add_node(GL const& g, u8 ch, u32 pos) {
+template <class G>
+__device__ __forceinline__ i32 pg_add_node(G const& g, u8 ch, u32 pos) {
   if (ST.nn >= g.pn) {
     ST.overflow = 1;
     return 0;
@@ -261,25 +306,27 @@ __device__ __forceinline__ i32 pg_add_node(GL const& g, u8 ch, u32 pos) {
 }
 // spoa::Graph::AddEdge (weights dropped).  Also used lane-parallel by the graph update: there every
 // call touches the out-list of a distinct tail and the in-list of a distinct head.
-__device__ __forceinline__ void pg_add_edge(GL const& g, u32 tail, u32 head, u32 lab) {
+template <class G>
+__device__ __forceinline__ void pg_add_edge(G const& g, u32 tail, u32 head, u32 lab) {
   u32 const no = g.nout[tail];
   for (u32 x = 0; x < no; ++x)
-    if (g.out_head[tail * kPE + x] == head) {
-      g.lab_or(tail * kPE + x, lab);
+    if (g.out_head[tail * G::pe + x] == head) {
+      g.lab_or(tail * G::pe + x, lab);
       return;
     }
   u32 const ni = g.nin[head];
-  if (no >= kPE || ni >= kPE) {
-    atomicOr(&ST.overflow, 1u);
+  if (no >= G::pe || ni >= G::pe) {
+    atomicOr(&ST.overflow, kOvSlots);
     return;
   }
-  g.out_head[tail * kPE + no] = static_cast<u16>(head);
-  g.lab_set(tail * kPE + no, lab);
+  g.out_head[tail * G::pe + no] = static_cast<u16>(head);
+  g.lab_set(tail * G::pe + no, lab);
   g.nout[tail] = static_cast<u8>(no + 1);
-  g.in_tail[head * kPE + ni] = static_cast<u16>(tail);
+  g.in_tail[head * G::pe + ni] = static_cast<u16>(tail);
   g.nin[head] = static_cast<u8>(ni + 1);
 }
-__device__ __forceinline__ i32 pg_add_sequence(GL const& g, const u8* seq, u32 begin, u32 end) {  // spoa::Graph::AddSequence
+template <class G>
+__device__ __forceinline__ i32 pg_add_sequence(G const& g, const u8* seq, u32 begin, u32 end) {  // spoa::Graph::AddSequence
   if (begin >= end) return -1;
   i32 prev = -1;
   u32 const first = ST.nn;
@@ -292,9 +339,10 @@ __device__ __forceinline__ i32 pg_add_sequence(GL const& g, const u8* seq, u32 b
   }
   return static_cast<i32>(first);
 }
-__device__ __forceinline__ i32 pg_successor(GL const& g, u32 node, u32 label) {  // spoa::Graph::Node::Successor
+template <class G>
+__device__ __forceinline__ i32 pg_successor(G const& g, u32 node, u32 label) {  // spoa::Graph::Node::Successor
   for (int x = 0; x < g.nout[node]; ++x)
-    if (g.lab(node * kPE + x) & (1u << label)) return static_cast<i32>(g.out_head[node * kPE + x]);
+    if (g.lab(node * G::pe + x) & (1u << label)) return static_cast<i32>(g.out_head[node * G::pe + x]);
   return -1;
 }
 // spoa::Graph::TopologicalSort, run by wave 0 (marks / ignored are zeroed by the caller).
@@ -302,7 +350,8 @@ __device__ __forceinline__ i32 pg_successor(GL const& g, u32 node, u32 label) { 
 // when root s is reached every node with a smaller id is already marked.  A root without aligned nodes
 // whose in-neighbours all have smaller ids is therefore ranked on the spot; runs of such roots (and of
 // already-marked ones) are handled 64 at a time with a ballot.  Every other root gets the serial DFS.
-__device__ __forceinline__ void pg_toposort(GL const& g, int lane) {
+template <class G>
+__device__ __forceinline__ void pg_toposort(G const& g, int lane) {
   u32 const nn = ST.nn;
   u32 nrank = 0, s = 0;
   u32 overflow = 0;
@@ -315,7 +364,7 @@ __device__ __forceinline__ void pg_toposort(GL const& g, int lane) {
       if (!marked && g.nal[v] == 0) {
         u32 const ni = g.nin[v];
         bool ok = true;
-        for (u32 x = 0; x < ni; ++x) ok = ok && g.in_tail[v * kPE + x] < v;
+        for (u32 x = 0; x < ni; ++x) ok = ok && g.in_tail[v * G::pe + x] < v;
         trivial = ok;
       }
     }
@@ -341,7 +390,7 @@ __device__ __forceinline__ void pg_toposort(GL const& g, int lane) {
         bool valid = true;
         if (g.marks[cur] != 2) {
           for (int x = 0; x < g.nin[cur]; ++x) {
-            u32 const t = g.in_tail[cur * kPE + x];
+            u32 const t = g.in_tail[cur * G::pe + x];
             if (g.marks[t] != 2) {
               if (sp < g.stack_cap) stack[sp++] = static_cast<u16>(t); else overflow = 1;
               valid = false;
@@ -349,7 +398,7 @@ __device__ __forceinline__ void pg_toposort(GL const& g, int lane) {
           }
           if (!g.ignored[cur]) {
             for (int x = 0; x < g.nal[cur]; ++x) {
-              u32 const an = g.al[cur * kPE + x];
+              u32 const an = g.al[cur * G::pe + x];
               if (g.marks[an] != 2) {
                 if (sp < g.stack_cap) stack[sp++] = static_cast<u16>(an); else overflow = 1;
                 g.ignored[an] = 1;
@@ -361,7 +410,7 @@ __device__ __forceinline__ void pg_toposort(GL const& g, int lane) {
             g.marks[cur] = 2;
             if (!g.ignored[cur]) {
               g.rank2node[nrank++] = static_cast<u16>(cur);
-              for (int x = 0; x < g.nal[cur]; ++x) g.rank2node[nrank++] = g.al[cur * kPE + x];
+              for (int x = 0; x < g.nal[cur]; ++x) g.rank2node[nrank++] = g.al[cur * G::pe + x];
             }
           } else {
             g.marks[cur] = 1;
@@ -415,9 +464,9 @@ __device__ __forceinline__ int bytes_cmp(const u8* a, u32 al, const u8* b, u32 b
 template <class G>
 __device__ __forceinline__ u32 pred_row(G const& g, u32 i, u32 info, u32 x) {
   if (info & RI_FAST) return i - 1;
-  if (info & RI_SLOWTAB) return g.slowpred[(info >> 16) * kPE + x];
+  if (info & RI_SLOWTAB) return g.slowpred[(G::pe <= 4 ? info >> 16 : (info >> 16) & 0xFFu) * G::pe + x];  // (eight slots: bit 24 is ri_np's)
   u32 const node = g.rank2node[i - 1];
-  return static_cast<u32>(g.node2rank[g.in_tail[node * kPE + x]]) + 1u;
+  return static_cast<u32>(g.node2rank[g.in_tail[node * G::pe + x]]) + 1u;
 }
 
 // closed forms of DP row 0 and DP column 0 (SisdAlignmentEngine::Initialize, kNW convex)
@@ -512,7 +561,7 @@ __device__ __forceinline__ i32 wave_incl_max(i32 x, i32 ident) {
 __device__ __forceinline__ i32 wave_shr1(i32 x, i32 ident) { return dpp_mov<0x138, 0xF>(x, ident); }  // wave_shr:1
 
 // Decision codes live in two byte planes of one window's code area: plane A (bits 0-5 of the code: move, extension
-// flags) is written for every row, plane B (bits 6-9: the predecessor indices) only for rows that are not FAST -- a FAST
+// flags) is written for every row, plane B (bits 6-9: the predecessor indices; 6-11 with eight slots, kXB) only for rows that are not FAST -- a FAST
 // row has a single predecessor, index 0.  Half the bytes of one u16 per cell, and the traceback reads plane B only when
 // it stands on such a row.
 template <int CW>
@@ -547,8 +596,8 @@ __device__ __forceinline__ void store_code_bytes(u8* dst, const u32 (&cd)[CW], u
 // (always inlined, like everything that takes the graph view or the workspace by reference: an out-of-line callee needs
 //  them in memory, and "memory" for a kernel argument is a private copy per thread -- half a KB of scratch stores by every
 //  thread of every workgroup at kernel entry, 1 GB per launch, and a scratch load behind every LDS offset in the callee)
-template <int CW>
-__device__ __forceinline__ void poa_fill(GL const& g, PoaWs const& ws, u16* codes, i32* rows, i32* hlast, u32 V, u32 L, int tid,
+template <int CW, class G>
+__device__ __forceinline__ void poa_fill(G const& g, PoaWs const& ws, u16* codes, i32* rows, i32* hlast, u32 V, u32 L, int tid,
                          const u8* seq) {
   static_assert(E_ == -2 && C_ == -1, "prefix-max keys are written for e = -2, c = -1");
   int const lane = tid & 63, wave = tid >> 6;
@@ -581,7 +630,7 @@ __device__ __forceinline__ void poa_fill(GL const& g, PoaWs const& ws, u16* code
 #ifdef MA_PROFILE
     unsigned long long const q0 = __builtin_amdgcn_s_memtime();
 #endif
-    u32 const nch = info & 0xFFu, np = (info >> 8) & 7u;
+    u32 const nch = info & 0xFFu, np = ri_np<G::pe>(info);
     bool const fast = info & RI_FAST, store = info & RI_STORE;
     u32 const info_cur = info;
     i32 const h0 = col0_h(depth);
@@ -786,7 +835,8 @@ __device__ __forceinline__ void poa_fill(GL const& g, PoaWs const& ws, u16* code
       }
       // second pass over the predecessors: which one SPOA's backtrack would pick, in its test order
       u32 dmask = 0, umask = 0, eumask = 0, usmask = 0, uhmask = 0;
-      u32 xs[CW];  // predecessor indices: [1:0] diagonal, [3:2] up, [5:4] F/O extension, [7:6] H extension
+      constexpr u32 XB = kXB<G::pe>, XM = (1u << XB) - 1u;
+      u32 xs[CW];  // predecessor indices, XB bits each (four slots: [1:0], eight: [2:0]) diagonal, up, F/O extension, H extension
 #pragma unroll
       for (int c = 0; c < CW; ++c) xs[c] = 0;
       for (u32 x = 0; x < npe; ++x) {
@@ -807,17 +857,17 @@ __device__ __forceinline__ void poa_fill(GL const& g, PoaWs const& ws, u16* code
           bool const t1 = h == a1, t2 = h == a2, t3 = h == a3, t4 = h == a4;
           if (!(umask & bit) && (t1 || t2 || t3 || t4)) {
             umask |= bit;
-            xs[c] |= x << 2;
+            xs[c] |= x << XB;
             if (t1 || (!t2 && t3)) eumask |= bit;
           }
           if (np) {  // a row without in-edges has an empty predecessor loop in the up-extension walk
             if (!(usmask & bit) && ((ff[c] == a1) || (oo[c] == a3))) {
               usmask |= bit;
-              xs[c] |= x << 4;
+              xs[c] |= x << (2 * XB);
             }
             if (!(uhmask & bit) && ((ff[c] == a2) || (oo[c] == a4))) {
               uhmask |= bit;
-              xs[c] |= x << 6;
+              xs[c] |= x << (3 * XB);
             }
           }
         }
@@ -831,8 +881,8 @@ __device__ __forceinline__ void poa_fill(GL const& g, PoaWs const& ws, u16* code
         code |= (lcmask & bit) ? 8u : 0u;
         bool const us = usmask & bit, uh = uhmask & bit;
         code |= us ? 16u : (uh ? 32u : 0u);
-        code |= (D ? (xs[c] & 3u) : (U ? ((xs[c] >> 2) & 3u) : 0u)) << 6;
-        code |= (us ? ((xs[c] >> 4) & 3u) : (uh ? ((xs[c] >> 6) & 3u) : 0u)) << 8;
+        code |= (D ? (xs[c] & XM) : (U ? ((xs[c] >> XB) & XM) : 0u)) << 6;
+        code |= (us ? ((xs[c] >> (2 * XB)) & XM) : (uh ? ((xs[c] >> (3 * XB)) & XM) : 0u)) << (6 + XB);
         cd[c] = code;
       }
     }
@@ -965,7 +1015,7 @@ __device__ void poa_fill_band(G const& g, u32 const w_stride, size_t const plane
   // split the rotation across the loop edge)
   auto row = [&](u32 const i, i32(&H1)[CW], i32(&F1)[CW], i32(&O1)[CW], i32(&H2)[CW], i32(&F2)[CW], i32(&O2)[CW])
                  __attribute__((always_inline)) {
-    u32 const nch = info & 0xFFu, np = (info >> 8) & 7u;
+    u32 const nch = info & 0xFFu, np = ri_np<G::pe>(info);
     bool const fast = info & RI_FAST, store = info & RI_STORE;
     u32 const info_cur = info;
     i32 const h0 = col0_h(depth);
@@ -1244,6 +1294,7 @@ __device__ void poa_fill_band(G const& g, u32 const w_stride, size_t const plane
         }
       }
       u32 dmask = 0, umask = 0, eumask = 0, usmask = 0, uhmask = 0;
+      constexpr u32 XB = kXB<G::pe>, XM = (1u << XB) - 1u;
       u32 xs[CW];
 #pragma unroll
       for (int c = 0; c < CW; ++c) xs[c] = 0;
@@ -1265,17 +1316,17 @@ __device__ void poa_fill_band(G const& g, u32 const w_stride, size_t const plane
           bool const t1v = h == a1v, t2v = h == a2v, t3v = h == a3v, t4v = h == a4v;
           if (!(umask & bit) && (t1v || t2v || t3v || t4v)) {
             umask |= bit;
-            xs[c] |= x << 2;
+            xs[c] |= x << XB;
             if (t1v || (!t2v && t3v)) eumask |= bit;
           }
           if (np) {
             if (!(usmask & bit) && ((ff[c] == a1v) || (oo[c] == a3v))) {
               usmask |= bit;
-              xs[c] |= x << 4;
+              xs[c] |= x << (2 * XB);
             }
             if (!(uhmask & bit) && ((ff[c] == a2v) || (oo[c] == a4v))) {
               uhmask |= bit;
-              xs[c] |= x << 6;
+              xs[c] |= x << (3 * XB);
             }
           }
         }
@@ -1289,8 +1340,8 @@ __device__ void poa_fill_band(G const& g, u32 const w_stride, size_t const plane
         code |= (lcmask & bit) ? 8u : 0u;
         bool const us = usmask & bit, uh = uhmask & bit;
         code |= us ? 16u : (uh ? 32u : 0u);
-        code |= (D ? (xs[c] & 3u) : (U ? ((xs[c] >> 2) & 3u) : 0u)) << 6;
-        code |= (us ? ((xs[c] >> 4) & 3u) : (uh ? ((xs[c] >> 6) & 3u) : 0u)) << 8;
+        code |= (D ? (xs[c] & XM) : (U ? ((xs[c] >> XB) & XM) : 0u)) << 6;
+        code |= (us ? ((xs[c] >> (2 * XB)) & XM) : (uh ? ((xs[c] >> (3 * XB)) & XM) : 0u)) << (6 + XB);
         cd[c] = code;
       }
     }
@@ -1533,7 +1584,7 @@ __device__ void poa_fill_lean(G const& g, u32 const w_stride, size_t const plane
 
   // ---- every other row: poa_fill_band's row with one register row ----
   auto row_gen = [&](u32 const i, u32 const info) __attribute__((always_inline)) {
-    u32 const nch = info & 0xFFu, np = (info >> 8) & 7u;
+    u32 const nch = info & 0xFFu, np = ri_np<G::pe>(info);
     bool const fast = info & RI_FAST, store = info & RI_STORE;
     i32 const h0 = col0_h(g.rowdepth[i]);
     u32 const j0_new = g.rowj0[i];
@@ -1719,6 +1770,7 @@ __device__ void poa_fill_lean(G const& g, u32 const w_stride, size_t const plane
       }
     }
     u32 dmask = 0, umask = 0, eumask = 0, usmask = 0, uhmask = 0;
+    constexpr u32 XB = kXB<G::pe>, XM = (1u << XB) - 1u;
     u32 xs[CW];
 #pragma unroll
     for (int c = 0; c < CW; ++c) xs[c] = 0;
@@ -1740,17 +1792,17 @@ __device__ void poa_fill_lean(G const& g, u32 const w_stride, size_t const plane
         bool const t1v = h == a1v, t2v = h == a2v, t3v = h == a3v, t4v = h == a4v;
         if (!(umask & bit) && (t1v || t2v || t3v || t4v)) {
           umask |= bit;
-          xs[c] |= x << 2;
+          xs[c] |= x << XB;
           if (t1v || (!t2v && t3v)) eumask |= bit;
         }
         if (np) {
           if (!(usmask & bit) && ((ff[c] == a1v) || (oo[c] == a3v))) {
             usmask |= bit;
-            xs[c] |= x << 4;
+            xs[c] |= x << (2 * XB);
           }
           if (!(uhmask & bit) && ((ff[c] == a2v) || (oo[c] == a4v))) {
             uhmask |= bit;
-            xs[c] |= x << 6;
+            xs[c] |= x << (3 * XB);
           }
         }
       }
@@ -1764,8 +1816,8 @@ __device__ void poa_fill_lean(G const& g, u32 const w_stride, size_t const plane
       code |= (lcmask & bit) ? 8u : 0u;
       bool const us = usmask & bit, uh = uhmask & bit;
       code |= us ? 16u : (uh ? 32u : 0u);
-      code |= (D ? (xs[c] & 3u) : (U ? ((xs[c] >> 2) & 3u) : 0u)) << 6;
-      code |= (us ? ((xs[c] >> 4) & 3u) : (uh ? ((xs[c] >> 6) & 3u) : 0u)) << 8;
+      code |= (D ? (xs[c] & XM) : (U ? ((xs[c] >> XB) & XM) : 0u)) << 6;
+      code |= (us ? ((xs[c] >> (2 * XB)) & XM) : (uh ? ((xs[c] >> (3 * XB)) & XM) : 0u)) << (6 + XB);
       cd[c] = code;
     }
     if (lane == 63 && jb + CW - 1 < L) edge = max(edge, hh[CW - 1]);
@@ -1845,7 +1897,8 @@ __device__ void poa_fill_lean(G const& g, u32 const w_stride, size_t const plane
 struct EdgeVals {
   i32 h, f, e, o, q;
 };
-__device__ __forceinline__ EdgeVals edge_vals(GL const& g, u32 i, u32 j) {  // cells of row 0 / column 0
+template <class G>
+__device__ __forceinline__ EdgeVals edge_vals(G const& g, u32 i, u32 j) {  // cells of row 0 / column 0
   EdgeVals v;
   if (i == 0 && j == 0) {
     v.h = v.f = v.e = v.o = v.q = 0;
@@ -1865,7 +1918,8 @@ __device__ __forceinline__ EdgeVals edge_vals(GL const& g, u32 i, u32 j) {  // c
 }
 
 // bw: columns of the band the codes were written for (64, 128 or 256); 0 = the full row-synchronous fill
-__device__ __forceinline__ u32 poa_traceback(GL const& g, const u16* codes16, size_t const plane, u32 cw, u32 V, u32 L, u32 best_row,
+template <class G>
+__device__ __forceinline__ u32 poa_traceback(G const& g, const u16* codes16, size_t const plane, u32 cw, u32 V, u32 L, u32 best_row,
                              bool have_end, int lane, u32 bw) {
   const u8* const codes = reinterpret_cast<const u8*>(codes16);
   bool const band = bw != 0;
@@ -1929,11 +1983,12 @@ __device__ __forceinline__ u32 poa_traceback(GL const& g, const u16* codes16, si
       }
       u32 const cd = code_at(i, j);
       u32 const info = g.rowinfo[i];
-      u32 const np = (info >> 8) & 7u;
+      u32 const np = ri_np<G::pe>(info);
       u32 const node = g.rank2node[i - 1];
       u32 const kind = cd & 3u;
       bool const ext = cd & 4u;
-      u32 const x = (cd >> 6) & 3u;
+      constexpr u32 XB = kXB<G::pe>, XM = (1u << XB) - 1u;
+      u32 const x = (cd >> 6) & XM;
       if (kind == 0) {
         prev_i = np ? pred_row(g, i, info, x) : 0u;
         prev_j = j - 1;
@@ -1971,7 +2026,7 @@ __device__ __forceinline__ u32 poa_traceback(GL const& g, const u16* codes16, si
             u32 const c2 = code_at(i, j);
             u32 const info2 = g.rowinfo[i];
             bool const us = c2 & 16u, uh = c2 & 32u;
-            u32 const pi = (us || uh) ? pred_row(g, i, info2, (c2 >> 8) & 3u) : 0u;
+            u32 const pi = (us || uh) ? pred_row(g, i, info2, (c2 >> (6 + XB)) & XM) : 0u;
             push1(g.rank2node[i - 1] + 1u, 0);
             prev_i = pi;
             i = pi;
@@ -2012,7 +2067,7 @@ __device__ __forceinline__ u32 poa_traceback(GL const& g, const u16* codes16, si
     bool found = false, ext_left = false, ext_up = false;
     u32 const node = i ? g.rank2node[i - 1] : 0u;
     u32 const info = i ? g.rowinfo[i] : 0u;
-    u32 const np = i ? ((info >> 8) & 7u) : 0u;
+    u32 const np = i ? (ri_np<G::pe>(info)) : 0u;
     if (i != 0) {
       for (u32 x = 0; x < (np ? np : 1u); ++x) {
         u32 const pi = np ? pred_row(g, i, info, x) : 0u;
@@ -2058,7 +2113,7 @@ __device__ __forceinline__ u32 poa_traceback(GL const& g, const u16* codes16, si
         prev_i = 0;
         u32 const nd2 = g.rank2node[i - 1];
         u32 const info2 = g.rowinfo[i];
-        u32 const np2 = (info2 >> 8) & 7u;
+        u32 const np2 = ri_np<G::pe>(info2);
         EdgeVals const cv = edge_vals(g, i, j);
         for (u32 x = 0; x < np2; ++x) {
           u32 const pr = pred_row(g, i, info2, x);
@@ -2105,7 +2160,8 @@ __device__ __forceinline__ u16 band_j0(u32 npos, u32 L, u32 cwb) {
 // Per-row flags of a band tier (after rowj0, RI_STORE and rowdepth are final): which rows take poa_fill_lean's
 // straight-line path, and the exits that are known before the fill (column 0 of a row is an exit when the row's window
 // does not start at column 1; its value is closed-form).
-__device__ __forceinline__ void band_flags(GL const& g, u32 V, u32 cwb, int tid) {
+template <class G>
+__device__ __forceinline__ void band_flags(G const& g, u32 V, u32 cwb, int tid) {
   int const lane = tid & 63, wave = tid >> 6;
   i32 e0 = kNegInf;
   for (u32 i = 1 + tid; i <= V; i += kT) {
@@ -2180,6 +2236,13 @@ __device__ __forceinline__ bool poa_window_skipped(MsaArgs const& A, int w) {
   bool wide = false;
   u32 const nc = A.a.win_ncomp[w];
   for (u32 c = 0; c < nc; ++c) wide = wide || A.a.comp_nhaps[static_cast<size_t>(w) * A.prm.max_comps + c] > 16;
+  if (A.ws.pass >= 3) {  // a retry pass: the windows k_poa_retry_select reset, by their cause and their widest component
+    u32 const cause = A.ws.cause[w];
+    if (!(cause & (kOvNodes | kOvSlots)) || (cause & kCauseLeft)) return true;
+    bool const width = (cause & kOvSlots) != 0;
+    if (width != (A.ws.pass <= 4)) return true;
+    return (wide || A.ws.len_all32) != (A.ws.pass == 4 || A.ws.pass == 6);
+  }
   return wide != (A.ws.pass == 2);
 }
 
@@ -2187,7 +2250,7 @@ __device__ __forceinline__ bool poa_window_skipped(MsaArgs const& A, int w) {
 // are in the image) or to its end (kMsaDone).  `resume`: continue from the image after a fill.  Runs as the body of k_msa
 // (host-counted rounds, MA_POA_SCHED=0) and as the G job of the persistent kernel k_poa.
 constexpr u32 kMsaDone = 0, kMsaYield = 1;
-template <int CWMAX, bool LAB32>
+template <int CWMAX, bool LAB32, int PE>
 __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool const resume_in) {
   int const tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int const w = A.win0 + lw;
@@ -2203,7 +2266,8 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
   }
   if (poa_window_skipped(A, w)) return kMsaDone;  // the other pass's window
   u32 const PN = ws.pn;
-  GL const g = poa_carve(PN, ws.max_l, LAB32 ? 1u : 0u);
+  using G = GLT<PE>;
+  G const g = poa_carve<PE>(PN, ws.max_l, LAB32 ? 1u : 0u);
   u16* const codes = reinterpret_cast<u16*>(reinterpret_cast<u8*>(ws.codes) + static_cast<size_t>(lw) * ws.code_cells * 2);
   i32* const rows = ws.rows + static_cast<size_t>(lw) * ws.row_cells;
   size_t const fslot = ws.full_by_worker ? static_cast<size_t>(blockIdx.x) : static_cast<size_t>(lw);
@@ -2214,7 +2278,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
   // the code area in HBM beyond that (every byte thread 0 reads back from HBM is a round trip of its serial walk)
   u8* const raw_hbm = reinterpret_cast<u8*>(codes);
   u8* const raw_lds = &ma_lds[g.rowinfo.off];
-  u32 const raw_lds_room = (static_cast<u32>(poa_lds_bytes(PN, ws.max_l, LAB32 ? 1u : 0u)) - 16u - g.rowinfo.off) / g.max_seq();  // bytes per haplotype
+  u32 const raw_lds_room = (static_cast<u32>(poa_lds_bytes(PN, ws.max_l, LAB32 ? 1u : 0u, PE)) - 16u - g.rowinfo.off) / g.max_seq();  // bytes per haplotype
   u32 const raw_lds_cap = ws.raw_cap ? min(ws.raw_cap, raw_lds_room) : raw_lds_room;
 
   // Split mode: the banded fill of an alignment runs in k_msa_band (one wavefront per window, a dozen windows per
@@ -2278,7 +2342,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
     u32 const hap0 = A.a.comp_hap0[ci], nh = A.a.comp_nhaps[ci];
     if (tid == 0 && !rc) {
       ST.nn = ST.nseq = ST.nrank = 0;
-      ST.overflow = nh > g.max_seq() ? 1u : 0u;  // label masks are 16 / 32 bit (launch_msa sends wider components to the LAB32 pass)
+      ST.overflow = nh > g.max_seq() ? kOvOther : 0u;  // label masks are 16 / 32 bit (launch_msa sends wider components to the LAB32 pass)
     }
     u32 const h_start = rc ? ST.h_cur : 0u;
     for (u32 h = h_start; h < nh; ++h) {
@@ -2331,9 +2395,9 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
           g.nin[i] = i > 0 ? 1 : 0;
           g.nout[i] = i + 1 < L ? 1 : 0;
           g.nal[i] = 0;
-          g.in_tail[i * kPE] = static_cast<u16>(i - 1);
-          g.out_head[i * kPE] = static_cast<u16>(i + 1);
-          g.lab_set(i * kPE, lab);
+          g.in_tail[i * G::pe] = static_cast<u16>(i - 1);
+          g.out_head[i * G::pe] = static_cast<u16>(i + 1);
+          g.lab_set(i * G::pe, lab);
           g.rank2node[i] = static_cast<u16>(i);
           g.node2rank[i] = static_cast<u16>(i);
           g.npos[i] = static_cast<u16>(i);
@@ -2430,15 +2494,15 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
       for (u32 i = 1 + tid; i <= V; i += kT) {
         u32 const node = g.rank2node[i - 1];
         u32 const np = g.nin[node];
-        u32 pr[kPE];
-        for (u32 x = 0; x < kPE; ++x) pr[x] = x < np ? static_cast<u32>(g.node2rank[g.in_tail[node * kPE + x]]) + 1u : 0u;
-        u32 info = static_cast<u32>(g.nchar[node]) | (np << 8);
+        u32 pr[G::pe];
+        for (u32 x = 0; x < G::pe; ++x) pr[x] = x < np ? static_cast<u32>(g.node2rank[g.in_tail[node * G::pe + x]]) + 1u : 0u;
+        u32 info = static_cast<u32>(g.nchar[node]) | ri_np_bits<G::pe>(np);
         if (np == 1 && pr[0] + 1 == i) {
           info |= RI_FAST;
         } else if (np > 0) {
           u32 const idx = atomicAdd(&ST.nslow, 1u);
           if (idx < kSlowCap) {
-            for (u32 x = 0; x < np; ++x) g.slowpred[idx * kPE + x] = static_cast<u16>(pr[x]);
+            for (u32 x = 0; x < np; ++x) g.slowpred[idx * G::pe + x] = static_cast<u16>(pr[x]);
             info |= RI_SLOWTAB | (idx << 16);
           }
         }
@@ -2485,7 +2549,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
           for (u32 k = 0; k < total_slow; ++k) {
             u32 const r = g.aln[k];
             u32 const inf = g.rowinfo[r];
-            u32 const np = (inf >> 8) & 7u;
+            u32 const np = ri_np<G::pe>(inf);
             u32 d = 0;
             if (np) {
               d = 0xFFFFu;
@@ -2711,7 +2775,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
               } else {
                 u32 const na = g.nal[jt];
                 for (u32 y = 0; y < na; ++y) {
-                  u32 const kt = g.al[jt * kPE + y];
+                  u32 const kt = g.al[jt * G::pe + y];
                   if (g.nchar[kt] == ch) {
                     cur = kt;
                     break;
@@ -2751,20 +2815,20 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
               if (grpmask & (1u << (v - vlo))) {  // join the aligned ring of node jt
                 u32 const jt = static_cast<u32>(g.cnode[v]) - 1;
                 u32 const na = g.nal[jt];
-                if (na + 1 > kPE) {
-                  atomicOr(&ST.overflow, 1u);
+                if (na + 1 > G::pe) {
+                  atomicOr(&ST.overflow, kOvSlots);
                   continue;
                 }
                 for (u32 y = 0; y < na; ++y) {
-                  u32 const kt = g.al[jt * kPE + y];
+                  u32 const kt = g.al[jt * G::pe + y];
                   u32 const nk = g.nal[kt];
-                  g.al[kt * kPE + nk] = static_cast<u16>(cur);
+                  g.al[kt * G::pe + nk] = static_cast<u16>(cur);
                   g.nal[kt] = static_cast<u8>(nk + 1);
-                  g.al[cur * kPE + y] = static_cast<u16>(kt);
+                  g.al[cur * G::pe + y] = static_cast<u16>(kt);
                 }
-                g.al[jt * kPE + na] = static_cast<u16>(cur);
+                g.al[jt * G::pe + na] = static_cast<u16>(cur);
                 g.nal[jt] = static_cast<u8>(na + 1);
-                g.al[cur * kPE + na] = static_cast<u16>(jt);
+                g.al[cur * G::pe + na] = static_cast<u16>(jt);
                 g.nal[cur] = static_cast<u8>(na + 1);
               }
             }
@@ -3016,7 +3080,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
         if (v + 1 < nn) {
           u32 const no = g.nout[v];
           for (u32 x = 0; x < no; ++x)
-            if (g.out_head[v * kPE + x] == v + 1 && (g.lab(v * kPE + x) & allmask) == allmask) ok = true;
+            if (g.out_head[v * G::pe + x] == v + 1 && (g.lab(v * G::pe + x) & allmask) == allmask) ok = true;
         }
         unsigned long long const m = __ballot(ok);
         u32 const cnt = m == ~0ull ? 64u : static_cast<u32>(__builtin_ctzll(~m));
@@ -3024,7 +3088,8 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
       }
       __syncthreads();
     }
-    if (tid == 0 && overflow) ST.win_overflow = 1;
+    // (bits 1 and up: what the GRAPH overflowed for, if it did -- a caller's cap leaves them 0; for PoaWs::cause below)
+    if (tid == 0 && overflow) ST.win_overflow = 1u | (ST.overflow << 1);
     PROF_ACC(5);
   }
   if (yielded) {  // save the LDS block; the next launch of this kernel resumes from it
@@ -3043,7 +3108,11 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
   }
   if (tid == 0) {
     A.o.win_nvars[w] = nvars;
-    if (overflow) A.a.win_status[w] |= MA_W_VAR_OVERFLOW;
+    if (overflow) {
+      A.a.win_status[w] |= MA_W_VAR_OVERFLOW;
+      // ma_set_poa_retry: why, for the retry passes (a retry pass adds its own cause to the first pass's mark)
+      if (ws.cause) ws.cause[w] = static_cast<u8>(ws.cause[w] | ((ST.win_overflow >> 1) & (kOvNodes | kOvSlots)));
+    }
     if (ws.split) {
       ST.done = 1;
       ST.pending = 0;
@@ -3056,9 +3125,9 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
   return kMsaDone;
 }
 
-template <int CWMAX, bool LAB32>
+template <int CWMAX, bool LAB32, int PE>
 __global__ __launch_bounds__(kT, LAB32 ? 1 : 2) void k_msa(MsaArgs A) {
-  (void)msa_window<CWMAX, LAB32>(A, static_cast<int>(blockIdx.x), A.round > 0);
+  (void)msa_window<CWMAX, LAB32, PE>(A, static_cast<int>(blockIdx.x), A.round > 0);
 }
 
 // The row descriptors of a pending alignment, read straight from the window's LDS image in HBM: every access is
@@ -3082,7 +3151,9 @@ struct ScalarArr {
     else return (w >> ((a & 3u) * 8u)) & 0xFFu;
   }
 };
+template <int PE_>
 struct DescView {
+  static constexpr int pe = PE_;
   ScalarArr<u32> rowinfo;
   ScalarArr<u16> rowslot, rowdepth, rowj0, slowpred;
   // only reached for rows without a cached predecessor list, which k_msa never hands over (nslow <= kSlowCap)
@@ -3101,7 +3172,7 @@ struct DescView {
 // (host-counted rounds) and the F job of the persistent kernel k_poa.  Nothing of the window is staged in LDS -- the state
 // block's few fields and the row descriptors come straight from the image in HBM -- so any wavefront of any workgroup can
 // run it; lut_off = 256 bytes of LDS of the wavefront's own for poa_fill_lean's code table.
-template <bool LEAN>
+template <bool LEAN, int PE>
 __device__ __forceinline__ bool band_job(MsaArgs const& A, int const lw, int const lane, u32 const lut_off) {
   int const w = A.win0 + lw;
   ma_params_t const& P = A.prm;
@@ -3110,9 +3181,9 @@ __device__ __forceinline__ bool band_job(MsaArgs const& A, int const lw, int con
   WgState* const pst = reinterpret_cast<WgState*>(img);
   if (pst->done || !pst->pending || pst->filled || pst->band == 0) return false;
   u32 const PN = ws.pn;
-  GL const full = poa_carve(PN, ws.max_l, ws.lab32);
+  GLT<PE> const full = poa_carve<PE>(PN, ws.max_l, ws.lab32);
   const u8* const ib = reinterpret_cast<const u8*>(img);
-  DescView g;
+  DescView<PE> g;
   g.rowinfo.base = reinterpret_cast<const u32*>(ib + full.rowinfo.off);
   g.rowslot.base = reinterpret_cast<const u16*>(ib + full.rowslot.off);
   g.rowdepth.base = reinterpret_cast<const u16*>(ib + full.rowdepth.off);
@@ -3155,11 +3226,11 @@ __device__ __forceinline__ bool band_job(MsaArgs const& A, int const lw, int con
   return true;
 }
 
-template <bool LEAN>
+template <bool LEAN, int PE>
 __global__ __launch_bounds__(64, 4) void k_msa_band(MsaArgs A) {
   int const lw = blockIdx.x;
   if (poa_window_skipped(A, A.win0 + lw)) return;
-  (void)band_job<LEAN>(A, lw, static_cast<int>(threadIdx.x), 16u);
+  (void)band_job<LEAN, PE>(A, lw, static_cast<int>(threadIdx.x), 16u);
 }
 
 // ---- the persistent POA kernel: device-side scheduling instead of host-counted rounds (round 6) ----------------------------
@@ -3357,7 +3428,7 @@ __global__ __launch_bounds__(kT, LAB32 ? 1 : 2) void k_poa(MsaArgs A, PoaSched* 
       if (static_cast<u32>(wave) < cnt) {
         int const lw = static_cast<int>(__builtin_amdgcn_readfirstlane(sh_job[2 + wave]));
         poa_acquire(dev_scope);  // the image another workgroup saved
-        (void)band_job<true>(A, lw, lane, static_cast<u32>(wave) * 256u);
+        (void)band_job<true, 4>(A, lw, lane, static_cast<u32>(wave) * 256u);
         poa_release(dev_scope);  // codes, stored rows, last column, edge maximum, the image's `filled`
         if (lane == 0) q_push(&D->g_tail, gq, qmask, static_cast<u32>(lw));
       }
@@ -3370,7 +3441,7 @@ __global__ __launch_bounds__(kT, LAB32 ? 1 : 2) void k_poa(MsaArgs A, PoaSched* 
     }
     int const lw = static_cast<int>(sh_job[2]);
     if (kind == 2) poa_acquire(dev_scope);  // the fill's outputs
-    u32 const st = msa_window<CWMAX, LAB32>(A, lw, kind == 2);
+    u32 const st = msa_window<CWMAX, LAB32, 4>(A, lw, kind == 2);
     if (st == kMsaYield) poa_release(dev_scope);  // the image (every wavefront wrote a part)
     __syncthreads();
     if (tid == 0) {
@@ -3446,6 +3517,45 @@ __global__ __launch_bounds__(256) void k_msa_maxima(ma_asm_out_t a, int n, u32 m
     if (mlw) atomic_max_lazy(&out[3], mlw);
   }
 }
+// ---- ma_set_poa_retry: the windows whose POA graph overflowed get a second pass with a larger graph ----
+// The counter block in front of the cause marks (ma_ctx::poa_cause), 16 u32: [0] windows marked for the slot width, [1] for the
+// node capacity only, [2] marked windows the retry passes called, [3] marked windows still MA_W_VAR_OVERFLOW after them,
+// [4 .. 7] longest haplotype of the windows of retry pass 3 .. 6 (PoaWs::pass), [8] most alignments of any of them.
+// Counts the marks and resets every marked window a retry pass can hold: a capped component leaves the variants of the
+// components before it behind and drops the later ones, so the window starts over at component 0 with win_nvars = 0 and its
+// flag cleared.  A window whose longest haplotype the pass it needs cannot hold with 32 spare nodes (caps: poa_retry_max_hap_len
+// of the width pass, 16- / 32-bit labels, then of the capacity pass) keeps its flag and its variants (kCauseLeft: the passes
+// step over it).
+struct RetryCaps {
+  u32 len[4];
+};
+__global__ __launch_bounds__(256) void k_poa_retry_select(ma_asm_out_t a, u32* win_nvars, int n, u32 max_haps, u32 max_comps, u8* cause,
+                                                          RetryCaps caps, u32 all32, u32* ctr) {
+  int const w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= n) return;
+  u32 const c = cause[w] & (kOvNodes | kOvSlots);
+  if (!c) return;
+  bool const width = (c & kOvSlots) != 0;
+  atomicAdd(&ctr[width ? 0 : 1], 1u);
+  u32 mh, al;
+  u32 const ml = window_longest_hap(a, w, max_haps, max_comps, &mh, &al);
+  bool const wide = all32 || mh > 16;
+  if (ml > caps.len[(width ? 0 : 2) + (wide ? 1 : 0)]) {
+    cause[w] = static_cast<u8>(c | kCauseLeft);
+    return;
+  }
+  win_nvars[w] = 0;
+  a.win_status[w] &= ~static_cast<u32>(MA_W_VAR_OVERFLOW);
+  atomicMax(&ctr[4 + (width ? 0 : 2) + (wide ? 1 : 0)], ml);
+  atomicMax(&ctr[8], al);
+}
+// ... and after the passes: which of the marked windows were called, which are flagged still (or again)
+__global__ __launch_bounds__(256) void k_poa_retry_count(ma_asm_out_t a, int n, const u8* cause, u32* ctr) {
+  int const w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= n || !(cause[w] & (kOvNodes | kOvSlots))) return;
+  atomicAdd(&ctr[(a.win_status[w] & MA_W_VAR_OVERFLOW) ? 3 : 2], 1u);
+}
+
 static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o);
 // The POA rounds of a lane are short launches of few, long-lived wavefronts (one per window): next to another lane's
 // throughput kernel -- thousands of workgroups queued for every wave slot -- each of their launches waits for slots like
@@ -3479,9 +3589,10 @@ int launch_msa(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var
   return rc;
 }
 static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o, u32 max_len, u32 rounds,
-                           u32 lab32, u32 pass, const u32 (&len_caps)[3]);
+                           u32 lab32, u32 pass, const u32 (&len_caps)[3], u8* cause);
 static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o) {
   int const n = b.n_windows;
+  for (auto& c : ctx->poa_retry_counts) c = 0;
   if (n == 0) return MA_OK;
   ma_params_t const& P = ctx->prm;
   if (P.max_haps > static_cast<int>(kMaxSeq)) {
@@ -3516,31 +3627,70 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
   bool const any_wide = got[2] > 16;
   bool const flagged = got[4] != 0;  // windows left out for their length: the passes have to step over them
   u32 const caps[3] = {flagged ? cap16 : 0u, cap32, all32 ? 1u : 0u};
-  if (all32) return launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u, caps);
-  // The reference has no cap on the haplotypes of a component (cbdg/graph.cpp:846-924, caller/msa_builder.cpp:29-42); the
-  // engine's is the caller's max_haps <= 32.  Components of up to 16 haplotypes take the common kernels (16-bit label masks,
-  // two workgroups per CU); a window with a wider component takes the LAB32 kernels in a pass of its own.
-  MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 0u, any_wide ? 1u : 0u, caps));
-  if (any_wide) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, std::max(got[3], 16u), rounds, 1u, 2u, caps));
+  // ma_set_poa_retry: the passes mark why a window's graph overflowed -- in a buffer of the context's own, cleared per call
+  // (with the counter block in front of it); off: no buffer, no fill, a null pointer to the kernels
+  u8* cause = nullptr;
+  u32* rctr = nullptr;
+  if (ctx->poa_retry) {
+    MA_HIP(ctx, ctx->poa_cause.reserve(64 + static_cast<size_t>(n)));
+    rctr = ctx->poa_cause.as<u32>();
+    cause = ctx->poa_cause.as<u8>() + 64;
+    MA_HIP(ctx, hipMemsetAsync(ctx->poa_cause.p, 0, 64 + static_cast<size_t>(n), ctx->stream));
+  }
+  if (all32) {
+    MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u, caps, cause));
+  } else {
+    // The reference has no cap on the haplotypes of a component (cbdg/graph.cpp:846-924, caller/msa_builder.cpp:29-42); the
+    // engine's is the caller's max_haps <= 32.  Components of up to 16 haplotypes take the common kernels (16-bit label masks,
+    // two workgroups per CU); a window with a wider component takes the LAB32 kernels in a pass of its own.
+    MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 0u, any_wide ? 1u : 0u, caps, cause));
+    if (any_wide) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, std::max(got[3], 16u), rounds, 1u, 2u, caps, cause));
+  }
+  if (!cause) return MA_OK;
+  static RetryCaps const rcaps{{poa_retry_max_hap_len(0u, 8u), poa_retry_max_hap_len(1u, 8u), poa_retry_max_hap_len(0u, 4u), poa_retry_max_hap_len(1u, 4u)}};
+  hipLaunchKernelGGL(k_poa_retry_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a, o.win_nvars, n, static_cast<u32>(P.max_haps),
+                     static_cast<u32>(P.max_comps), cause, rcaps, all32 ? 1u : 0u, rctr);
+  u32 marks[4] = {0, 0, 0, 0};
+  MA_HIP(ctx, hipMemcpyAsync(marks, rctr, 16, hipMemcpyDeviceToHost, ctx->stream));
+  MA_HIP(ctx, ma_stream_sync(ctx));
+  ctx->poa_retry_counts[0] = marks[0];
+  ctx->poa_retry_counts[1] = marks[1];
+  if (marks[0] + marks[1] == 0) return MA_OK;
+  u32 mx[5] = {0, 0, 0, 0, 0};  // longest haplotype of each retry pass's windows, most alignments of any
+  MA_HIP(ctx, hipMemcpyAsync(mx, rctr + 4, 20, hipMemcpyDeviceToHost, ctx->stream));
+  MA_HIP(ctx, ma_stream_sync(ctx));
+  u32 const rrounds = std::max<u32>(1u, mx[4] + 1u);
+  // the width pass (eight slots per node), then the capacity pass (four, the block's LDS in nodes); each over the windows with
+  // 16-bit label masks and over those that need 32
+  for (u32 k = 0; k < 4; ++k)
+    if (mx[k]) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, mx[k], rrounds, k & 1u, 3u + k, caps, cause));
+  hipLaunchKernelGGL(k_poa_retry_count, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a, n, static_cast<const u8*>(cause), rctr);
+  MA_HIP(ctx, hipMemcpyAsync(marks, rctr, 16, hipMemcpyDeviceToHost, ctx->stream));
+  MA_HIP(ctx, ma_stream_sync(ctx));
+  ctx->poa_retry_counts[2] = marks[2];
+  ctx->poa_retry_counts[3] = marks[3];
   return MA_OK;
 }
 static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o, u32 max_len, u32 rounds,
-                           u32 const lab32, u32 const pass, const u32 (&len_caps)[3]) {
+                           u32 const lab32, u32 const pass, const u32 (&len_caps)[3], u8* const cause) {
   int const n = b.n_windows;
   ma_params_t const& P = ctx->prm;
   PoaWs ws{};
   MA_TRY_RC(ma_dev_stats(ctx, &ws.dstats));
   ws.lab32 = lab32;
   ws.pass = pass;
+  ws.cause = cause;
+  bool const retry = pass >= 3;                       // a retry pass: the node capacity maxed out, host-counted rounds
+  u32 const pe = (pass == 3 || pass == 4) ? 8u : 4u;  // ... and for the width pass eight slots per node
   ws.len_cap16 = len_caps[0];
   ws.len_cap32 = len_caps[1];
   ws.len_all32 = len_caps[2];
   max_len = std::max<u32>(max_len, 16);
   ws.max_l = max_len;
   // two workgroups per CU when the graph fits in 80 KB of LDS, one otherwise
-  u32 const pn = poa_node_capacity(max_len, lab32);
-  size_t const lds = poa_lds_bytes(pn, max_len, lab32);
-  if (lds > kPoaLdsLimit) {  // (not reached: k_msa_maxima has left the windows out that are longer than poa_max_hap_len)
+  u32 const pn = retry ? poa_node_capacity_max(max_len, lab32, pe) : poa_node_capacity(max_len, lab32);
+  size_t const lds = poa_lds_bytes(pn, max_len, lab32, pe);
+  if (pn == 0 || lds > kPoaLdsLimit) {  // (not reached: k_msa_maxima has left the windows out that are longer than poa_max_hap_len)
     ma_set_err(ctx, "ma_msa_batch: haplotypes too long for the LDS-resident POA graph");
     return MA_ERR_PARAM;
   }
@@ -3581,7 +3731,8 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   ws.img_words = static_cast<u32>(ws.split ? img_bytes / 4 : ws.img_words);
   // MA_POA_SCHED: 1 (default) = the persistent kernel k_poa schedules the windows on the device; 0 = rounds 3-5's host-counted
   // rounds of k_msa / k_msa_band (same device code: msa_window, band_job; same results, tested)
-  bool const sched = ws.split && ws.lean && !(getenv("MA_POA_SCHED") && atoi(getenv("MA_POA_SCHED")) == 0);
+  // (a retry pass takes the host-counted rounds: a handful of windows, and the persistent kernel is not built for eight slots)
+  bool const sched = !retry && ws.split && ws.lean && !(getenv("MA_POA_SCHED") && atoi(getenv("MA_POA_SCHED")) == 0);
   ws.full_by_worker = sched ? 1u : 0u;
   // workgroups of the persistent kernel: what the chip holds at once (two per CU while the graph fits 80 KB of LDS; a lane
   // that runs beside others may be told to take one -- MA_POA_WGS_PER_CU -- and leave the other half of every CU's LDS to them)
@@ -3613,8 +3764,10 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   if (getenv("MA_VERBOSE"))
     fprintf(stderr, "[microasm] msa: %d windows, %.2f MB/window + %zu full-fill areas of %.2f MB, budget %.1f GB -> chunks of %d (pn %u, max_len %u, lds %zu)\n",
             n, per_window / 1048576.0, max_workers, full_bytes / 1048576.0, budget / 1073741824.0, chunk, pn, max_len, lds);
-  auto kern = lab32 ? (max_len <= 1024 ? k_msa<4, true> : (max_len <= 2048 ? k_msa<8, true> : k_msa<16, true>))
-                    : (max_len <= 1024 ? k_msa<4, false> : (max_len <= 2048 ? k_msa<8, false> : k_msa<16, false>));
+  auto kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 4> : (max_len <= 2048 ? k_msa<8, true, 4> : k_msa<16, true, 4>))
+                    : (max_len <= 1024 ? k_msa<4, false, 4> : (max_len <= 2048 ? k_msa<8, false, 4> : k_msa<16, false, 4>));
+  if (pe == 8)  // (poa_retry_max_hap_len(*, 8) < 2048: the widest column tier is never needed)
+    kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 8> : k_msa<8, true, 8>) : (max_len <= 1024 ? k_msa<4, false, 8> : k_msa<8, false, 8>);
   MA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   static_cast<int>(lds)));
   auto pkern = lab32 ? (max_len <= 1024 ? k_poa<4, true> : (max_len <= 2048 ? k_poa<8, true> : k_poa<16, true>))
@@ -3713,8 +3866,14 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
         }
         ctx->tic("k_msa_band");
         auto band = [&](auto kfn) { hipLaunchKernelGGL(kfn, dim3(nwin), dim3(64), band_lds, ctx->stream, args); };
-        if (ws.lean) band(k_msa_band<true>);  // (first tiers, retried fills and haplotypes that start wide alike)
-        else band(k_msa_band<false>);
+        if (pe == 8) {
+          if (ws.lean) band(k_msa_band<true, 8>);
+          else band(k_msa_band<false, 8>);
+        } else if (ws.lean) {
+          band(k_msa_band<true, 4>);  // (first tiers, retried fills and haplotypes that start wide alike)
+        } else {
+          band(k_msa_band<false, 4>);
+        }
         ctx->toc();
       }
     }

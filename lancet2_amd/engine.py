@@ -49,6 +49,9 @@ def load_library(path=None):
     lib.ma_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     lib.ma_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     lib.ma_set_streams.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(lib, "ma_set_poa_retry"):  # (likewise: a build of before the POA retry passes)
+        lib.ma_set_poa_retry.argtypes = capi.SET_POA_RETRY_ARGTYPES
+        lib.ma_last_poa_retry.argtypes = capi.LAST_POA_RETRY_ARGTYPES
     return lib
 
 
@@ -99,6 +102,17 @@ class Engine:
     def set_streams(self, n):
         """Number of concurrent window ranges ma_process_batch uses (0 = automatic)."""
         self._check(self.lib.ma_set_streams(self.h, n), "ma_set_streams")
+
+    def set_poa_retry(self, on):
+        """1: windows whose POA graph overflowed are re-run by a second pass with a larger graph (include/microasm.h:
+        ma_set_poa_retry); 0 (the default): they stay MA_W_VAR_OVERFLOW."""
+        self._check(self.lib.ma_set_poa_retry(self.h, int(on)), "ma_set_poa_retry")
+
+    def last_poa_retry(self):
+        """Counts of include/microasm.h:ma_last_poa_retry for the last call that ran the POA stage."""
+        buf = (C.c_ulonglong * 4)()
+        n = self.lib.ma_last_poa_retry(self.h, buf, 4)
+        return {k: int(buf[i]) for i, k in enumerate(capi.POA_RETRY_KEYS) if i < n}
 
     def stats(self):
         """Work counters of include/microasm.h:ma_last_stats."""
