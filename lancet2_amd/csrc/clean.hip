@@ -2256,6 +2256,7 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
     }
     size_t const cidx = static_cast<size_t>(w) * MC + ncomp_out;
     u32 const hap0 = slot;
+    u32 ref_wgt = 1u;
     CSUB_ACC(11);
     // REF haplotype (graph.cpp:902-924)
     {
@@ -2272,6 +2273,7 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
       wave_sync_mem(g.lds);
       sort_small_u32(confs, ncf, g.lds);
       u32 const wgt = ncf == 0 ? 1u : median_sorted(confs, ncf);
+      ref_wgt = wgt;
       size_t const hi = static_cast<size_t>(w) * MH + slot;
       u32 len = anchor_len;
       if (len > static_cast<u32>(ML)) {
@@ -2304,11 +2306,12 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
     bool has_alt = false;
     for (int oi = 0; oi < nwalks; ++oi) {
       int const wi = order[oi];
-      if (static_cast<int>(slot) >= MH) {
-        status |= MA_W_HAP_OVERFLOW;
-        break;
-      }
-      size_t const hi = static_cast<size_t>(w) * MH + slot;
+      // The reference counts a component's haplotypes AFTER it dropped the walks that repeat an earlier one or spell the REF
+      // anchor (graph.cpp:883-887), so a walk that finds every row of the window taken overflows only if it would be kept.
+      // Row max_haps is the next window's (or lies behind the caller's buffer): such a walk is spelled into the component's
+      // REF row, compared from there -- the REF row's own content is read from the anchor instead -- and the row is put back.
+      bool const full = static_cast<int>(slot) >= MH;
+      size_t const hi = static_cast<size_t>(w) * MH + (full ? hap0 : slot);
       u8* hb = A.out.hap_bases + hi * ML;
       u32* covs = g.scratch;  // node coverages in walk order
       u32 ncov = 0, pos = 0, nruns = 0;
@@ -2392,6 +2395,8 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
         pos = carry;
         ncov = wl + 1u;
         nruns = wl + 1u;
+        // (above, a lane learns of the cap only if ITS node is beyond it; the flag below is the wavefront's, lane 0 included)
+        runs_ok = nruns <= static_cast<u32>(MR);
         wave_sync_mem(true);
         if (__ballot(pover)) {
           g.flags |= 4u;  // more slices than the piece table holds: k_clean has the window again
@@ -2447,11 +2452,22 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
         for (u32 h = hap0; h < slot && !dup; ++h) {
           size_t const oi2 = static_cast<size_t>(w) * MH + h;
           if (A.out.hap_len[oi2] != pos) continue;
-          const u8* ob = A.out.hap_bases + oi2 * ML;
+          const u8* ob = h == hap0 ? ref_anchor : A.out.hap_bases + oi2 * ML;  // (the REF row is a copy of the anchor)
           bool diff = false;
           for (u32 x = lane; x < pos; x += 64) diff |= ob[x] != hb[x];
           dup = __ballot(diff) == 0;
         }
+      }
+      if (full) {
+        u32 const len0 = anchor_len < static_cast<u32>(ML) ? anchor_len : static_cast<u32>(ML);
+        __threadfence_block();
+        for (u32 x = lane; x < len0; x += 64) hb[x] = ref_anchor[x];
+        A.out.hap_runs[(hi * MR) * 2 + 0] = ref_wgt;
+        A.out.hap_runs[(hi * MR) * 2 + 1] = anchor_len;
+        __threadfence_block();
+        if (dup) continue;
+        status |= MA_W_HAP_OVERFLOW;
+        break;
       }
       if (dup) continue;
       if (!ok || !runs_ok) status |= MA_W_LEN_OVERFLOW;

@@ -279,6 +279,18 @@ int orc_assemble_batch(const ma_params_t* prm, const ma_batch_t* b, const ma_asm
   return 0;
 }
 
+// Test tap: what became of every max-flow walk of window w's components, in the order the dedup sees them (graph.cpp,
+// BuildHaplotypes): one line per component of the result, one letter per walk -- K kept, r equals the REF anchor, d duplicate
+// of an earlier walk.  Returns the number of components, or -1 when buf (cap bytes, NUL-terminated) is too small.
+int orc_walk_dispositions(const ma_params_t* prm, const ma_batch_t* b, int w, char* buf, int cap) {
+  AssemblyResult const res = BuildComponentResults(WindowRef(b, w), WindowReads(b, w), ToParams(prm));
+  std::string t;
+  for (auto const& c : res.comps) t += c.walk_fates + "\n";
+  if (static_cast<int>(t.size()) + 1 > cap) return -1;
+  std::memcpy(buf, t.c_str(), t.size() + 1);
+  return static_cast<int>(res.comps.size());
+}
+
 namespace {
 struct CompView {
   std::vector<std::string> haps;

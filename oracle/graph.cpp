@@ -181,7 +181,7 @@ class Graph {
   static bool HasCycle(const TraversalIndex& idx);
   GraphComplexity ComputeComplexity(u32 comp) const;
   std::vector<Haplotype> BuildHaplotypes(u32 comp, const TraversalIndex& idx,
-                                         std::string_view ref_anchor, bool* hit_limit) const;
+                                         std::string_view ref_anchor, bool* hit_limit, std::string* fates) const;
   Haplotype BuildRefHaplotype(u32 comp, std::string_view ref_anchor) const;
 };
 
@@ -575,7 +575,7 @@ Haplotype Graph::BuildRefHaplotype(u32 comp, std::string_view ref_anchor) const 
 
 // cbdg/max_flow.cpp:162-280 + graph.cpp:846-891
 std::vector<Haplotype> Graph::BuildHaplotypes(u32 comp, const TraversalIndex& idx,
-                                              std::string_view ref_anchor, bool* hit_limit) const {
+                                              std::string_view ref_anchor, bool* hit_limit, std::string* fates) const {
   std::vector<Haplotype> haps;
   std::vector<u8> traversed(idx.orig_edges.size(), 0);
   struct WalkNode { u32 ordinal, dst_state, parent, score; };
@@ -657,6 +657,7 @@ std::vector<Haplotype> Graph::BuildHaplotypes(u32 comp, const TraversalIndex& id
   std::unordered_set<std::string> seen;
   for (auto& h : haps) {
     bool const inserted = seen.insert(h.seq).second;
+    fates->push_back(h.seq == ref_anchor ? 'r' : inserted ? 'K' : 'd');
     if (!inserted || h.seq == ref_anchor) continue;
     kept.push_back(std::move(h));
   }
@@ -712,7 +713,8 @@ AssemblyResult Graph::Run() {
         break;
       }
       bool hit = false;
-      auto haps = BuildHaplotypes(ci.id, tidx, ref_anchor, &hit);
+      std::string fates;
+      auto haps = BuildHaplotypes(ci.id, tidx, ref_anchor, &hit, &fates);
       attempt_limit = attempt_limit || hit;
       if (dbg) fprintf(stderr, "[orc] haps=%zu cc=%llu bp=%llu\n", haps.size(), (unsigned long long)cx.cyclomatic, (unsigned long long)cx.branch_points);
       if (haps.empty()) continue;
@@ -721,6 +723,7 @@ AssemblyResult Graph::Run() {
       cr.metrics = cx;
       cr.anchor_start = static_cast<u32>(src.off);
       cr.hit_bfs_limit = hit;
+      cr.walk_fates = std::move(fates);
       out.comps.push_back(std::move(cr));
     }
     if (retry) out.comps.clear();

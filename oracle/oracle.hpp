@@ -55,6 +55,7 @@ struct ComponentResult {
   GraphComplexity metrics;
   u32 anchor_start = 0;
   bool hit_bfs_limit = false;
+  std::string walk_fates;  // test tap: one letter per max-flow walk in MinWeight order, K kept / r equals the REF anchor / d duplicate
   // MaxAltPathCv (component_result.cpp:50-58): -1 when there is no ALT haplotype.
   f64 MaxAltPathCv() const;
 };

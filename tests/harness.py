@@ -32,6 +32,8 @@ def _declare(lib):
     lib.orc_refpos_to_qpos.restype = C.c_uint64
     lib.orc_entropy.restype = C.c_float
     lib.orc_longdust.restype = C.c_double
+    lib.orc_walk_dispositions.restype = C.c_int
+    lib.orc_walk_dispositions.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_int]
     return lib
 
 
@@ -121,17 +123,25 @@ def variants_of(p, var, w):
     return res
 
 
-def compare_asm(p, got, want, n):
-    """Bit-exact comparison of the used part of two ma_asm_out_t buffers; returns list of mismatch strings."""
+def _window_list(n, windows):
+    return list(range(n)) if windows is None else sorted(int(w) for w in windows)
+
+
+def compare_asm(p, got, want, n, windows=None):
+    """Bit-exact comparison of the used part of two ma_asm_out_t buffers; returns list of mismatch strings.
+    windows: an iterable of the windows to compare (default: all n)."""
     bad = []
+    ws = _window_list(n, windows)
+    sel = np.asarray(ws, dtype=np.int64)
     for name in ("win_status", "win_k", "win_ncomp"):
-        if not np.array_equal(got[name], want[name]):
-            idx = np.nonzero(got[name] != want[name])[0][:5]
+        g, x = got[name][sel], want[name][sel]
+        if not np.array_equal(g, x):
+            idx = sel[np.nonzero(g != x)[0][:5]]
             bad.append(f"{name} differs at windows {idx.tolist()}: got {got[name][idx].tolist()} want {want[name][idx].tolist()}")
     if bad:
         return bad
     MC, MH, ML, MR = p.max_comps, p.max_haps, p.max_hap_len, p.max_runs
-    for w in range(n):
+    for w in ws:
         for c in range(int(want["win_ncomp"][w])):
             ci = w * MC + c
             for name, width in (("comp_anchor", 1), ("comp_hap0", 1), ("comp_nhaps", 1), ("comp_cx", 3), ("comp_cxf", 4)):
@@ -154,12 +164,15 @@ def compare_asm(p, got, want, n):
     return bad
 
 
-def compare_vars(p, got, want, n):
+def compare_vars(p, got, want, n, windows=None):
+    """windows: an iterable of the windows to compare (default: all n)"""
     bad = []
-    if not np.array_equal(got["win_nvars"], want["win_nvars"]):
-        return [f"win_nvars got {got['win_nvars'].tolist()} want {want['win_nvars'].tolist()}"]
+    ws = _window_list(n, windows)
+    sel = np.asarray(ws, dtype=np.int64)
+    if not np.array_equal(got["win_nvars"][sel], want["win_nvars"][sel]):
+        return [f"win_nvars of windows {ws} got {got['win_nvars'][sel].tolist()} want {want['win_nvars'][sel].tolist()}"]
     MH, MV, MA, MP = p.max_haps, p.max_vars, p.max_alts, p.max_allele_bytes
-    for w in range(n):
+    for w in ws:
         nv = int(want["win_nvars"][w])
         for name, width in (("var_comp", 1), ("var_pos", 1), ("var_ref_start", 1), ("var_ref_off", 1), ("var_ref_len", 1),
                             ("var_nalts", 1), ("var_hap_allele", MH), ("var_hap_start", MH)):
@@ -216,10 +229,16 @@ def compare_geno(p, got, want, n, nr, win_nvars, read_win_off):
     return bad
 
 
-def compare_geno_calls(got, want):
+def compare_geno_calls(got, want, windows=None, n=None):
     """The call-level outputs of the genotype stage (what a caller that does not ask for the debug taps gets): allele
-    depths, PL, GQ equal; QUAL within 1e-9."""
+    depths, PL, GQ equal; QUAL within 1e-9.
+    windows: an iterable of the windows to compare, of the n windows of the batch (default: all)."""
     bad = []
+    if windows is not None:
+        sel = np.asarray(_window_list(n, windows), dtype=np.int64)
+        rows = lambda a: np.asarray(a).reshape(n, -1)[sel].reshape(-1)  # noqa: E731
+        got = {k: rows(got[k]) for k in ("allele_counts", "var_pl", "var_gq", "var_qual")}
+        want = {k: rows(want[k]) for k in ("allele_counts", "var_pl", "var_gq", "var_qual")}
     for key in ("allele_counts", "var_pl", "var_gq"):
         if not np.array_equal(got[key], want[key]):
             i = np.nonzero(got[key] != want[key])[0][:8]
