@@ -9,6 +9,7 @@
 //             (--packed-reads: the ma_*_packed_batch pair on 4-bit read bases and qualities, half the bytes over the link)
 //             (--read-meta with --out-vcf: ma_prefetch_meta_batch, and that call with the reads' MAPQ, clip and pair flags,
 //              insert size and start -- RMQ, SCA, FLD, RPCD, MQCD, FSSE are printed too: 24 of 24 FORMAT values)
+//             (--out-graphs-dir DIR: debugging -- the batch once more through ma_assemble_graph_batch, one DOT file per component)
 //   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
 // Build (no HIP headers needed; zlib only for BAM input):
@@ -175,6 +176,73 @@ void DumpBatch(const std::string& dir, FlatBatch const& fb) {
   put("windows.u64", wins.data(), 8 * wins.size());
 }
 
+// --out-graphs-dir: the batch once more through ma_assemble_graph_batch, one DOT file per exported component.  The caps start
+// at the binding's defaults; windows that come back flagged (MA_G_*) are re-submitted once -- the batch again, with the
+// largest reported needs as caps; a component that still has no graph then is named on stderr.  The arrays are sized
+// batch windows x caps on the host and again in the engine's staging: 62 KB per window at the first caps (1 GB at
+// --batch-windows 16384), more on a re-submission -- a debugging mode, run it on the regions in question with batches of a few
+// hundred windows.  Returns the number of files written, -1 when a call failed.
+struct GraphArrays {
+  std::vector<uint32_t> u32;
+  std::vector<uint8_t> u8;
+  ma_graph_out_t g{};
+  void Allocate(const ma_params_t& p, int n, int32_t mn, int32_t me, int32_t ms) {
+    size_t const N = n, S = p.num_samples, MN = mn, ME = me, MS = ms;
+    u32.assign(4 * N + 3 * N * MN + N * MN * S + 2 * N * ME, 0);
+    u8.assign(3 * N * MN + N * ME + N * MS, 0);
+    uint32_t* u = u32.data();
+    uint8_t* b = u8.data();
+    auto tu = [&](size_t c) { uint32_t* r = u; u += c; return r; };
+    auto tb = [&](size_t c) { uint8_t* r = b; b += c; return r; };
+    g.max_nodes = mn; g.max_edges = me; g.max_seq_bytes = ms;
+    g.win_gstatus = tu(N); g.win_nnodes = tu(N); g.win_nedges = tu(N); g.win_nseq = tu(N);
+    g.node_comp = tu(N * MN); g.node_seq_off = tu(N * MN); g.node_len = tu(N * MN); g.node_cnt = tu(N * MN * S);
+    g.node_sign = tb(N * MN); g.node_label = tb(N * MN); g.node_flags = tb(N * MN);
+    g.edge_src = tu(N * ME); g.edge_dst = tu(N * ME); g.edge_kind = tb(N * ME);
+    g.seq_pool = tb(N * MS);
+  }
+};
+
+long WriteGraphs(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& ref, FlatBatch const& fb, std::string const& dir) {
+  int const n = fb.view.n_windows;
+  Outputs o;
+  o.Allocate(prm, n, false);
+  GraphArrays ga;
+  int32_t caps[3] = {512, 2048, 32768};
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    ga.Allocate(prm, n, caps[0], caps[1], caps[2]);
+    if (ma_assemble_graph_batch(ctx, &fb.view, &o.asmb, &ga.g) != MA_OK) return -1;
+    bool flagged = false;
+    for (int w = 0; w < n; ++w) {
+      flagged = flagged || ga.g.win_gstatus[w] != 0;
+      caps[0] = std::max<int32_t>(caps[0], static_cast<int32_t>(ga.g.win_nnodes[w]));
+      caps[1] = std::max<int32_t>(caps[1], static_cast<int32_t>(ga.g.win_nedges[w]));
+      caps[2] = std::max<int32_t>(caps[2], static_cast<int32_t>(ga.g.win_nseq[w]));
+    }
+    if (!flagged) break;
+  }
+  long written = 0;
+  for (int w = 0; w < n; ++w) {
+    auto const& win = fb.windows[static_cast<size_t>(w)];
+    for (uint32_t c = 0; c < o.asmb.win_ncomp[w]; ++c) {
+      std::string const name = ref.chroms[static_cast<size_t>(win.chrom)].name + "_" + std::to_string(win.start1) + "_" + std::to_string(win.end1) +
+                               "__c" + std::to_string(c) + "__k" + std::to_string(o.asmb.win_k[w]);
+      std::string const dot = RenderComponentDot(prm, o.asmb, ga.g, w, c, o.asmb.win_k[w], name);
+      if (dot.empty()) {  // still flagged after the re-submission (the needs are the batch's largest: not expected), or no node
+        std::fprintf(stderr, "pipeline_driver: --out-graphs-dir: no graph for %s (export status %u: needs %u nodes, %u edges, %u bases)\n",
+                     name.c_str(), ga.g.win_gstatus[w], ga.g.win_nnodes[w], ga.g.win_nedges[w], ga.g.win_nseq[w]);
+        continue;
+      }
+      FILE* f = std::fopen((dir + "/" + name + ".dot").c_str(), "w");
+      if (!f) { std::perror("--out-graphs-dir"); return -1; }
+      std::fputs(dot.c_str(), f);
+      std::fclose(f);
+      ++written;
+    }
+  }
+  return written;
+}
+
 AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed) {
   bool const bam = path.size() > 4 && path.substr(path.size() - 4) == ".bam";
 #ifdef LANCET2_AMD_WITH_ZLIB
@@ -204,7 +272,7 @@ int main(int argc, char** argv) {
   //  in force -- ADVICE r5; the flat arrays are far below 32 MiB)
   if (mallopt(M_MMAP_THRESHOLD, 32 << 20) != 1 || mallopt(M_TRIM_THRESHOLD, 1 << 30) != 1 || mallopt(M_TOP_PAD, 64 << 20) != 1)
     std::fprintf(stderr, "pipeline_driver: mallopt rejected a setting; large arrays fall back to mmap (slower, still correct)\n");
-  std::string ref_path, out_path, dump_dir, vcf_path, command_line;
+  std::string ref_path, out_path, dump_dir, vcf_path, command_line, graphs_dir;
   for (int i = 0; i < argc; ++i) command_line += std::string(i ? " " : "") + argv[i];
   double gc_frac = 0.41;  // --genome-gc-bias of the reference CLI: background GC of the LongdustQ null model
   std::vector<std::string> normals, tumors, regions;
@@ -241,6 +309,7 @@ int main(int argc, char** argv) {
     else if (a == "--batch-windows") batch_windows = std::max(1, std::atoi(next()));
     else if (a == "--extract-threads") extract_threads = std::max(1, std::atoi(next()));  // (the reference: -T, one collector per worker)
     else if (a == "--dump") dump_dir = next();
+    else if (a == "--out-graphs-dir") graphs_dir = next();  // debugging: one DOT file per assembled component (assembles twice)
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
     else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
@@ -254,6 +323,11 @@ int main(int argc, char** argv) {
                          "                  sequence bytes are copied undecoded, SAM text is packed.  A base letter that is none of BAM's\n"
                          "                  =ACMGRSVTWYHKDBN (lower case included) becomes N, as in a BAM file; without the flag it is passed on\n"
                          "                  as it is.  Not with --collect-reads / --extract-pairs\n"
+                         "  --out-graphs-dir DIR  a debugging mode that ASSEMBLES EVERY BATCH TWICE: after a batch's chained call the batch goes\n"
+                         "                  through ma_assemble_graph_batch and DIR/<chrom>_<start>_<end>__c<comp>__k<k>.dot is written for every\n"
+                         "                  component a window reported -- the pruned graph its haplotypes were walked on.  Not with --packed-reads.\n"
+                         "                  Costs 62 KB of host memory per window of a batch (and as much on the device), more when windows\n"
+                         "                  outgrow the first caps and the batch is re-submitted: keep --batch-windows at a few hundred\n"
                          "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
                          "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
                          "                  all 24 FORMAT values.  Without it those six are \".\"\n"
@@ -263,6 +337,10 @@ int main(int argc, char** argv) {
   }
   if (packed_reads && (collect_reads || rp.extract_pairs)) {
     std::fprintf(stderr, "pipeline_driver: --packed-reads needs the flat collector (not with --collect-reads / --extract-pairs)\n");
+    return 2;
+  }
+  if (packed_reads && !graphs_dir.empty()) {  // (the stage calls do not take the packed form: include/microasm.h)
+    std::fprintf(stderr, "pipeline_driver: --out-graphs-dir needs ASCII reads (not with --packed-reads)\n");
     return 2;
   }
   rp.packed_reads = packed_reads;
@@ -545,6 +623,7 @@ int main(int argc, char** argv) {
   });
   // ---- stage 2: engine ----
   bool const with_meta = read_meta && !vcf_path.empty();
+  size_t n_graph_files = 0;
   std::thread engine([&] {
     Job j;
     while (to_engine.Pop(&j)) {
@@ -572,6 +651,15 @@ int main(int argc, char** argv) {
                             : ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
                                                      nullptr);  // (null: ma_process_batch)
       if (j.rc != MA_OK) j.err = ma_last_error(ctx);
+      if (j.rc == MA_OK && !graphs_dir.empty()) {
+        long const nf = WriteGraphs(ctx, prm, ref, *j.batch, graphs_dir);
+        if (nf < 0) {
+          j.rc = MA_ERR_HIP;
+          j.err = std::string("--out-graphs-dir: ") + ma_last_error(ctx);
+        } else {
+          n_graph_files += static_cast<size_t>(nf);
+        }
+      }
       busy_engine += secs(Clock::now() - t0);
       to_flush.Push(std::move(j));
     }
@@ -646,6 +734,7 @@ int main(int argc, char** argv) {
                "pipeline_driver: %zu windows (%zu N-only, %zu max-k repeat, %zu inactive, %zu below anchor coverage), %zu assembled, "
                "%zu with a capacity flag, %zu records\n",
                windows.size(), n_skipped[1], n_skipped[2], n_skipped[3], n_skipped[4], n_assembled, n_flagged, n_records);
+  if (!graphs_dir.empty()) std::fprintf(stderr, "pipeline_driver: %zu component graphs written to %s\n", n_graph_files, graphs_dir.c_str());
   double const wall = secs(Clock::now() - t_start);
   size_t blocks = 0;
   bool any_indexed = false;

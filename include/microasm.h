@@ -408,6 +408,59 @@ int ma_set_poa_retry(ma_ctx_t* ctx, int on);
  * All zero while the setting is off.  Returns the number of entries written. */
 int ma_last_poa_retry(ma_ctx_t* ctx, unsigned long long* out, int cap);
 
+/* ---- graph export: the pruned graph every reported component came from ------------------------------------------------ */
+/* What the reference draws per component of the reported k attempt with --out-graphs-tgz (cbdg/graph.cpp:216-223,
+ * BufferFinalSnapshot): for every window, the components that have a row in comp_* at the reported attempt win_k -- every
+ * alive node of the component and every edge stored on those nodes, in the state ComputeComponentComplexity and
+ * BuildHaplotypes see (graph.cpp:186-216): after PruneComponent, before and unchanged by the walk search.  comp_cx, comp_cxf,
+ * hap_runs and hap_stats are functions of exactly these nodes and edges.
+ * NOT exported: components that yielded no walk (the reference draws those as `fully_pruned`; they have no row in comp_*),
+ * and attempts that were retried at a larger k -- only the rung that produced the window's result leaves anything.  Windows
+ * without a result (win_ncomp == 0) have all four counts 0.  For a window whose win_status carries MA_W_TABLE_OVERFLOW,
+ * MA_W_HAP_OVERFLOW or MA_W_LEN_OVERFLOW the export is unspecified beyond staying inside the caps.
+ * Node order within a window is deterministic (a component's nodes keep the order of the engine's node arrays, the
+ * components of a window interleave) but otherwise unspecified: key nodes by sequence -- the node sequences of a component
+ * are distinct.  node_label: bit 0 = REFERENCE, bit 1 = read of a normal (CTRL) sample, bit 2 = read of a tumour (CASE) sample
+ * -- the engine's own bits.  A node's sequence is stored in its default orientation; a walk spells a node as stored when it
+ * arrives over an edge whose sign on the node's side is PLUS, and reverse complemented otherwise (max_flow.cpp:64-113).
+ * The counts always hold the NEED.  If a need exceeds its cap the window gets the matching ma_gstatus bit and none of its
+ * rows is defined; a write never passes a cap; re-submit with the reported need.  win_status is never touched by the export.
+ * With the export asked for, the call climbs the k ladder rung by rung (what MA_NO_SPEC selects) instead of attempting the
+ * last rungs six at a time; the two ladders give the same results.  Single lane, like every stage call. */
+enum ma_gstatus { MA_G_NODE_OVERFLOW = 1u << 0, MA_G_EDGE_OVERFLOW = 1u << 1, MA_G_SEQ_OVERFLOW = 1u << 2 };
+typedef struct ma_graph_out {
+  int32_t max_nodes, max_edges, max_seq_bytes;   /* caller's caps, per window */
+  uint32_t* win_gstatus;  /* [n] ma_gstatus */
+  uint32_t* win_nnodes;   /* [n] the NEED, also when it exceeds the cap */
+  uint32_t* win_nedges;   /* [n] likewise */
+  uint32_t* win_nseq;     /* [n] likewise: bytes of node sequence */
+  /* per node, stride max_nodes */
+  uint32_t* node_comp;    /* component slot c < win_ncomp[w]: the row of comp_* it belongs to */
+  uint32_t* node_seq_off; /* into the window's seq_pool */
+  uint32_t* node_len;
+  uint32_t* node_cnt;     /* [.. * num_samples] per-sample read support (Node::mCounts after merges) */
+  uint8_t*  node_sign;    /* 1 = PLUS: sign of the stored (default) sequence */
+  uint8_t*  node_label;   /* Label bits as the engine keeps them: bit 0 = REFERENCE */
+  uint8_t*  node_flags;   /* bit 0 source anchor, bit 1 sink anchor of its component */
+  /* per stored directed edge, stride max_edges (mirror edges both present, as on the nodes); the edges of a node are
+   * contiguous, in the node's list order, nodes in slot order */
+  uint32_t* edge_src; uint32_t* edge_dst;   /* node slots of this window */
+  uint8_t*  edge_kind;    /* 0 ++, 1 +-, 2 -+, 3 --  (source sign, destination sign) */
+  uint8_t*  seq_pool;     /* [n * max_seq_bytes] default-orientation sequences, ASCII */
+} ma_graph_out_t;
+/* ma_assemble_batch + the export.  gx == NULL IS ma_assemble_batch: the same kernels, nothing allocated.  Otherwise every
+ * array of gx is required (MA_ERR_ARG) and every cap must be >= 1 (MA_ERR_PARAM).  Both memory spaces: with MA_MEM_DEVICE the
+ * arrays of gx are device pointers (the struct itself is always in host memory).  The assembly outputs are byte for byte
+ * those of ma_assemble_batch on the same batch.  One more kernel per pass (k_graph_export) writes the rows of the windows
+ * that pass reported, from the arrays the clean kernels leave behind. */
+int ma_assemble_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* out, const ma_graph_out_t* gx);
+/* Windows whose rows the last ma_assemble_graph_batch wrote, by the clean route that reported them:
+ *   out[0] small LDS tail image   out[1] large LDS tail image   out[2] HBM tail   out[3] k_clean
+ * A window flagged MA_G_* is not counted (only its needs were written).  A window that a capacity retry pass assembles again
+ * after an earlier pass had reported it with components counts once per pass that wrote its rows.
+ * Returns the number of entries written. */
+int ma_last_graph_export(ma_ctx_t* ctx, unsigned long long* out, int cap);
+
 /* Work counters accumulated over the same region as ma_last_kernel_times (reset by ma_timing_control):
  *   out[0] read x haplotype pairs seen by ma_genotype_batch      out[1] pairs that needed the DP
  *   out[2] windows passed to ma_assemble_batch                   out[3] k attempts x windows assembled

@@ -180,6 +180,35 @@ def cx_out_spec(p, n):
                 seq_cx_d=(np.float64, n * MV * 3), graph_cx=(np.float64, n * MV * 3))
 
 
+MA_G_NODE_OVERFLOW, MA_G_EDGE_OVERFLOW, MA_G_SEQ_OVERFLOW = 1, 2, 4
+GRAPH_EXPORT_KEYS = ("tail_small", "tail_large", "tail_hbm", "clean")  # ma_last_graph_export: windows exported per route
+GRAPH_LABEL_REFERENCE = 1  # node_label bit 0 (bit 1: CTRL read, bit 2: CASE read)
+
+
+class GraphOut(C.Structure):
+    """ma_graph_out_t: the three caps, then fifteen arrays -- all required"""
+    _fields_ = [(n, C.c_int32) for n in ("max_nodes", "max_edges", "max_seq_bytes")] + [(n, C.c_void_p) for n in (
+        "win_gstatus", "win_nnodes", "win_nedges", "win_nseq", "node_comp", "node_seq_off", "node_len", "node_cnt",
+        "node_sign", "node_label", "node_flags", "edge_src", "edge_dst", "edge_kind", "seq_pool")]
+
+
+def graph_out_spec(p, n, max_nodes, max_edges, max_seq_bytes):
+    """arrays of ma_graph_out_t for n windows at the given per-window caps (ma_assemble_graph_batch)"""
+    S, MN, ME, MS = p.num_samples, max_nodes, max_edges, max_seq_bytes
+    return dict(win_gstatus=(np.uint32, n), win_nnodes=(np.uint32, n), win_nedges=(np.uint32, n), win_nseq=(np.uint32, n),
+                node_comp=(np.uint32, n * MN), node_seq_off=(np.uint32, n * MN), node_len=(np.uint32, n * MN),
+                node_cnt=(np.uint32, n * MN * S), node_sign=(np.uint8, n * MN), node_label=(np.uint8, n * MN),
+                node_flags=(np.uint8, n * MN), edge_src=(np.uint32, n * ME), edge_dst=(np.uint32, n * ME),
+                edge_kind=(np.uint8, n * ME), seq_pool=(np.uint8, n * MS))
+
+
+def make_graph_struct(arrays, max_nodes, max_edges, max_seq_bytes):
+    """ma_graph_out_t over a dict of arrays (numpy, torch tensors or raw pointers; kept alive by the caller)"""
+    s = fill_struct(GraphOut, {k: v for k, v in arrays.items() if k not in ("max_nodes", "max_edges", "max_seq_bytes")})
+    s.max_nodes, s.max_edges, s.max_seq_bytes = int(max_nodes), int(max_edges), int(max_seq_bytes)
+    return s
+
+
 def gate_out_spec(n):
     return dict(max_approx=(np.uint32, n), max_exact=(np.uint32, n))
 

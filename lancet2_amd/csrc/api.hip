@@ -12,7 +12,7 @@
 #include <thread>
 #include <unordered_map>
 
-#include "ma_internal.h"
+#include "graph_ws.h"
 #include "pack.h"
 #include "evidence.h"
 
@@ -100,6 +100,18 @@ std::vector<OutField> cx_fields(const ma_params_t& p, int n) {
   size_t const N = n, MV = p.max_vars;
   return {{off_of(&ma_cx_out_t::seq_cx_i), 4 * N * MV * 4}, {off_of(&ma_cx_out_t::seq_cx_f), 4 * N * MV * 4},
           {off_of(&ma_cx_out_t::seq_cx_d), 8 * N * MV * 3}, {off_of(&ma_cx_out_t::graph_cx), 8 * N * MV * 3}};
+}
+
+std::vector<OutField> graph_fields(const ma_params_t& p, int n, const ma_graph_out_t& g) {
+  size_t const N = n, S = p.num_samples, MN = g.max_nodes, ME = g.max_edges, MS = g.max_seq_bytes;
+  return {{off_of(&ma_graph_out_t::win_gstatus), 4 * N}, {off_of(&ma_graph_out_t::win_nnodes), 4 * N},
+          {off_of(&ma_graph_out_t::win_nedges), 4 * N}, {off_of(&ma_graph_out_t::win_nseq), 4 * N},
+          {off_of(&ma_graph_out_t::node_comp), 4 * N * MN}, {off_of(&ma_graph_out_t::node_seq_off), 4 * N * MN},
+          {off_of(&ma_graph_out_t::node_len), 4 * N * MN}, {off_of(&ma_graph_out_t::node_cnt), 4 * N * MN * S},
+          {off_of(&ma_graph_out_t::node_sign), N * MN}, {off_of(&ma_graph_out_t::node_label), N * MN},
+          {off_of(&ma_graph_out_t::node_flags), N * MN}, {off_of(&ma_graph_out_t::edge_src), 4 * N * ME},
+          {off_of(&ma_graph_out_t::edge_dst), 4 * N * ME}, {off_of(&ma_graph_out_t::edge_kind), N * ME},
+          {off_of(&ma_graph_out_t::seq_pool), N * MS}};
 }
 
 void*& ptr_at(void* strct, size_t off) { return *reinterpret_cast<void**>(static_cast<char*>(strct) + off); }
@@ -1302,6 +1314,7 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->pack_aux.release();
   ctx->ws_unpack.release();
   ctx->ws_sort.release();
+  ctx->gx_mark.release(); ctx->gx_routes.release();
   ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
@@ -1492,6 +1505,56 @@ int ma_assemble_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* ou
   MA_TRY(a.download(ctx));
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
   return MA_OK;
+}
+
+int ma_assemble_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* out, const ma_graph_out_t* gx) {
+  if (!gx) return ma_assemble_batch(ctx, b, out);  // the plain call: the same kernels, nothing allocated
+  MA_BEGIN(ctx);
+  if (!out) return MA_ERR_ARG;
+  if (!gx->win_gstatus || !gx->win_nnodes || !gx->win_nedges || !gx->win_nseq || !gx->node_comp || !gx->node_seq_off ||
+      !gx->node_len || !gx->node_cnt || !gx->node_sign || !gx->node_label || !gx->node_flags || !gx->edge_src || !gx->edge_dst ||
+      !gx->edge_kind || !gx->seq_pool)
+    return MA_ERR_ARG;
+  if (gx->max_nodes < 1 || gx->max_edges < 1 || gx->max_seq_bytes < 1) return MA_ERR_PARAM;
+  DBatch d;
+  MA_TRY(stage_batch(ctx, b, &d));
+  OutMirror<ma_asm_out_t> a;
+  MA_TRY(a.prepare(ctx, out, asm_fields(ctx->prm, d.n_windows), 2, false));
+  OutMirror<ma_graph_out_t> g;
+  MA_TRY(g.prepare(ctx, gx, graph_fields(ctx->prm, d.n_windows, *gx), 56, false));
+  g.dev.max_nodes = gx->max_nodes;
+  g.dev.max_edges = gx->max_edges;
+  g.dev.max_seq_bytes = gx->max_seq_bytes;
+  // the marks of a pass's slots (at most every window of the batch) and the four route counters
+  MA_HIP(ctx, ctx->gx_mark.reserve(sizeof(u32) * kGxMark * (static_cast<size_t>(d.n_windows) + 1)));
+  MA_HIP(ctx, ctx->gx_routes.reserve(4 * sizeof(unsigned long long)));
+  MA_HIP(ctx, hipMemsetAsync(ctx->gx_routes.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  GxDev const dev{g.dev, ctx->gx_mark.as<u32>(), ctx->gx_routes.as<unsigned long long>()};
+  MA_HIP(ctx, ctx->ws_misc.reserve(8ull * (d.n_windows + 1)));
+  u32* approx = ctx->ws_misc.as<u32>();
+  u32* exact = approx + d.n_windows;
+  MA_TRY(launch_gate(ctx, d, approx, exact));
+  ctx->gx = &dev;
+  int const rc = launch_assemble(ctx, d, a.dev, approx);
+  ctx->gx = nullptr;
+  MA_TRY(rc);
+  MA_TRY(a.download(ctx));
+  MA_TRY(g.download(ctx));
+  if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
+  return MA_OK;
+}
+
+int ma_last_graph_export(ma_ctx_t* ctx, unsigned long long* out, int cap) {
+  if (!ctx || !out) return MA_ERR_ARG;
+  unsigned long long h[4] = {0, 0, 0, 0};
+  if (ctx->gx_routes.p) {  // (no exporting call yet: zeros)
+    MA_HIP(ctx, hipSetDevice(ctx->device));
+    MA_HIP(ctx, hipMemcpyAsync(h, ctx->gx_routes.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(ctx, ma_stream_sync(ctx));
+  }
+  int n = 0;
+  for (; n < cap && n < 4; ++n) out[n] = h[n];
+  return n;
 }
 
 int ma_msa_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* out) {

@@ -401,6 +401,9 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
   hipLaunchKernelGGL(k_init_out, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, out, win_flags, n, static_cast<u32>(P.max_comps),
                      static_cast<u32>(P.max_haps));
   hipLaunchKernelGGL(k_flag_long_reads, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, b, out, win_flags);
+  // a call that exports the graphs (ma_assemble_graph_batch): every window starts with nothing exported; k_graph_export fills
+  // in the windows a pass reports (clean.hip: run_clean_pass)
+  if (ctx->gx) MA_TRY_RC(run_graph_export_clear(ctx, *ctx->gx, out.win_status, n, false));
 
   // capacity planning: instance maxima at the smallest k (the largest instance counts)
   ws.k = P.min_k;
@@ -543,6 +546,8 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
     if (pass > 0) {
       if (getenv("MA_NO_CAP_RETRY")) break;  // tests: show what a pass leaves flagged
       MA_HIP(ctx, hipMemsetAsync(counters + 10, 0, 8, ctx->stream));
+      // (the windows this pass assembles again take their export with them: it follows the pass that reports the window)
+      if (ctx->gx) MA_TRY_RC(run_graph_export_clear(ctx, *ctx->gx, out.win_status, n, true));
       hipLaunchKernelGGL(k_reset_overflowed, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, out, win_flags, n, counters + 10);
       u32 host_over[2] = {0, 0};  // windows to re-assemble, and those among them that a common-route-only pass handed over
       MA_HIP(ctx, hipMemcpyAsync(host_over, counters + 10, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -596,7 +601,8 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
         ws.active = active;
         if (host_cnt[1] == 0) break;  // every window of the chunk is resolved (graph.cpp:106 loop exit)
         if (!nested && kpass >= 1 && ws.n_active > 0 && static_cast<u32>(ws.n_active) <= kSpecPending && P.max_k > P.min_k &&
-            !getenv("MA_NO_SPEC")) {
+            !getenv("MA_NO_SPEC") && !ctx->gx) {  // (an exporting call keeps to the rung-by-rung ladder: the nested pass's outputs
+                                                  //  go through k_spec_select's field table, which carries no export rows)
           // few windows are left on the ladder: their next rungs at once (speculate_tail), until none is pending
           u32 still = 0;
           MA_TRY_RC(speculate_tail(ctx, b, out, gate_approx, active, static_cast<u32>(ws.n_active), win_flags, counters + 8, &still));

@@ -1363,17 +1363,44 @@ __device__ __forceinline__ u32 label_components(Win& g, u32* lab, u32* cid, u32 
   return ncomp_all;
 }
 
+// This file is compiled twice.  On its own it is the clean stage of every call: kGx is false and every `if constexpr (kGx)`
+// below is gone before code generation, so the kernels are instruction for instruction what they were before the graph
+// export existed (their register and LDS figures: DESIGN.md section 4).  clean_gx.hip includes it with MA_CLEAN_GX defined:
+// the same kernels under the names k_clean_gx / k_clean_tail_gx, for a call that exports the graphs (ma_assemble_graph_batch).
+// Those note, per component that got a row of comp_*, its component id and its two anchors in the slot's mark record
+// (graph_ws.h: kGxMark) and, once the window is reported, the row count and the route; the LDS kernels also write their final
+// image back to the cg_* arrays -- what k_graph_export (graph_export.hip) goes by.
+#ifdef MA_CLEAN_GX
+constexpr bool kGx = true;
+#define MA_GX_NAME(x) x##_gx
+#else
+constexpr bool kGx = false;
+#define MA_GX_NAME(x) x
+#endif
+
 struct CleanArgs {
   DBatch b;
   GraphWs ws;
   ma_asm_out_t out;
   ma_params_t prm;
+#ifdef MA_CLEAN_GX
+  u32* gx_mark;  // [n_active][kGxMark]
+#endif
 };
+// the mark record of slot a (only ever evaluated where kGx holds)
+__device__ __forceinline__ u32* gx_mark_of(CleanArgs const& A, int a) {
+#ifdef MA_CLEAN_GX
+  return A.gx_mark + static_cast<size_t>(a) * kGxMark;
+#else
+  return nullptr;
+#endif
+}
 
 // LDS of the one-wavefront kernels: the shared 8 KB table plus everything that used to be a dynamically indexed local
 // (candidate components, accepted walks, the edge order of EnqueueOutgoingEdges): as private arrays those lived in
 // scratch memory -- an HBM round trip per access of an already serial loop, 1.6 KB per lane.
 constexpr int kMaxCand = 16;
+constexpr u32 kTailSmallLink = 320;  // TailSmall::Link, below: how the candidate loop of an exporting call tells the two LDS images apart
 template <u32 kLink>
 struct CleanLdsT {
   u32 link[kLink];
@@ -1387,7 +1414,7 @@ using CleanLds = CleanLdsT<kLinkCap>;
 template <class SH>
 __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH& sh, int a, int w, int ncand, int first_phase, u32 NC);
 
-__global__ __launch_bounds__(64, 2) void k_clean(CleanArgs A) {  // (the rare route: registers rather than occupancy, no spills)
+__global__ __launch_bounds__(64, 2) void MA_GX_NAME(k_clean)(CleanArgs A) {  // (the rare route: registers rather than occupancy, no spills)
   int const a = blockIdx.x;
   u32 const lane = threadIdx.x;
   GraphWs const& ws = A.ws;
@@ -2504,6 +2531,14 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
     A.out.comp_cxf[cidx * 4 + 1] = cx_cv;
     A.out.comp_cxf[cidx * 4 + 2] = cx_tip;
     A.out.comp_cxf[cidx * 4 + 3] = has_alt ? max_alt_cv : -1.0;
+    if constexpr (kGx) {
+      if (lane == 0) {
+        u32* const mark = gx_mark_of(A, a);
+        mark[1 + 3 * ncomp_out + 0] = comp;
+        mark[1 + 3 * ncomp_out + 1] = static_cast<u32>(g.source);
+        mark[1 + 3 * ncomp_out + 2] = static_cast<u32>(g.sink);
+      }
+    }
     ncomp_out++;
   }
 
@@ -2544,6 +2579,33 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
   A.out.win_ncomp[w] = ncomp_out;
   A.out.win_status[w] = status;
   if (lane == 0) atomicOr(&ws.win_flags[w], 1u);
+  if constexpr (kGx) {
+    u32 const route = !compact ? kGxRouteClean : (!g.lds ? kGxRouteHbm : (g.link_cap == kTailSmallLink ? kGxRouteSmall : kGxRouteLarge));
+    if (lane == 0) gx_mark_of(A, a)[0] = ncomp_out | ((route + 1u) << 8);  // (zero before: run_clean_pass clears the pass's marks)
+    if (g.lds) {
+      // The export reads the pruned graph from the cg_* arrays: the final LDS image goes back to where k_clean_tail loaded
+      // it from -- the mirror of its load loops, plus the alive flags and the slice lists, which only exist in LDS on this
+      // route.  Base strings are not written back: cg_bsrc / cg_blen / cg_bsign still describe them (the image had moved
+      // the k-mers of untouched nodes into its own pool).  cg_comp and cg_sign never change.
+      wave_sync_mem(true);
+      size_t const nb = static_cast<size_t>(a) * ws.vc;
+      u32 const V = g.n;
+      int const S = g.S;
+      for (u32 i = lane; i < V * static_cast<u32>(S); i += 64) ws.cg_cnt[nb * S + i] = g.cnt[i];
+      for (u32 i = lane; i < V * kCgEdgeCap; i += 64) ws.cg_edge[nb * kCgEdgeCap + i] = g.edge[i];
+      for (u32 i = lane; i < V; i += 64) {
+        ws.cg_len[nb + i] = g.len[i];
+        ws.cg_label[nb + i] = g.label[i];
+        ws.cg_nedge[nb + i] = g.nedge[i];
+        ws.cg_alive[nb + i] = g.alive[i];
+        ws.cg_head[nb + i] = g.head[i];
+        ws.cg_tail[nb + i] = g.tail[i];
+        ws.cg_snext[nb + i] = g.snext[i];
+        ws.cg_sprev[nb + i] = g.sprev[i];
+        ws.cg_sdesc[nb + i] = g.sdesc[i];
+      }
+    }
+  }
 }
 
 // The candidate loop on the COMPACT graph k_clean_chains left: a few dozen nodes whose base strings are original k-mers
@@ -2555,7 +2617,7 @@ __device__ __forceinline__ void clean_candidates(CleanArgs const& A, Win& g, SH&
 // of which seven share a CU; the large one takes four.  The kernel is latency bound with one wavefront per window, so the
 // windows in flight per CU set its speed.
 struct TailSmall {
-  static constexpr u32 V = 64, Arena = 192, Link = 320, S = 2, Ek = 2, Wk = 5, Pieces = 127, Pool = 3072;
+  static constexpr u32 V = 64, Arena = 192, Link = kTailSmallLink, S = 2, Ek = 2, Wk = 5, Pieces = 127, Pool = 3072;
 };
 struct TailLarge {
   static constexpr u32 V = 128, Arena = 320, Link = 640, S = 4, Ek = 2, Wk = 5, Pieces = 255, Pool = 5120;
@@ -2581,7 +2643,7 @@ __device__ __forceinline__ bool tail_fits(u32 V, u32 pool_used, u32 kk, int S) {
 }
 
 template <class C, bool kLds>
-__global__ __launch_bounds__(64, 2) void k_clean_tail(CleanArgs A) {
+__global__ __launch_bounds__(64, 2) void MA_GX_NAME(k_clean_tail)(CleanArgs A) {
   int const a = blockIdx.x;
   u32 const lane = threadIdx.x;
   GraphWs const& ws = A.ws;
@@ -2743,9 +2805,22 @@ __global__ __launch_bounds__(64, 2) void k_clean_tail(CleanArgs A) {
 
 int run_clean_chains(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_params_t& prm);  // chains.hip
 
+#ifdef MA_CLEAN_GX
+// the pass of a call that exports the graphs: the same launches through this build's kernels, the marks of the pass's slots
+// cleared first, and k_graph_export behind k_clean -- before the next pass reuses the workspace
+int run_clean_pass_gx(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm_out_t& out) {
+  if (ws.n_active == 0) return MA_OK;
+  const GxDev* const gx = ctx->gx;
+  MA_HIP(ctx, hipMemsetAsync(gx->mark, 0, sizeof(u32) * kGxMark * static_cast<size_t>(ws.n_active), ctx->stream));
+  CleanArgs args{b, ws, out, ctx->prm, gx->mark};
+#else
+int run_clean_pass_gx(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm_out_t& out);  // clean_gx.hip
+
 int run_clean_pass(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm_out_t& out) {
   if (ws.n_active == 0) return MA_OK;
+  if (ctx->gx) return run_clean_pass_gx(ctx, b, ws, out);
   CleanArgs args{b, ws, out, ctx->prm};
+#endif
   bool const use_chains = !getenv("MA_NO_CHAINS");  // (read per call: the tests switch routes inside one process)
   if (use_chains && ws.cg_state) {
     // the first CompressGraph of every candidate component as bulk-parallel LDS work, then the rest of the candidate loop
@@ -2755,13 +2830,13 @@ int run_clean_pass(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm
     // k_clean_tail, the first readers are the kernels launched below -- build.hip, k_select_active)
     MA_TRY_RC(run_clean_chains(ctx, b, ws, ctx->prm));
     ctx->tic("k_clean_tail");
-    hipLaunchKernelGGL((k_clean_tail<TailSmall, true>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
+    hipLaunchKernelGGL((MA_GX_NAME(k_clean_tail)<TailSmall, true>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
     ctx->toc();
     ctx->tic("k_clean_tail");
-    hipLaunchKernelGGL((k_clean_tail<TailLarge, true>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
+    hipLaunchKernelGGL((MA_GX_NAME(k_clean_tail)<TailLarge, true>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
     ctx->toc();
     ctx->tic("k_clean_tail");
-    hipLaunchKernelGGL((k_clean_tail<TailHbm, false>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
+    hipLaunchKernelGGL((MA_GX_NAME(k_clean_tail)<TailHbm, false>), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
     ctx->toc();
   }  // (without the chains route cg_state stays what k_select_active left: 0, every window is k_clean's)
   if (use_chains && ws.cg_state && getenv("MA_VERBOSE")) {  // which windows fall through to k_clean, and how large they are
@@ -2786,9 +2861,12 @@ int run_clean_pass(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ma_asm
             ws.n_active, fall, fall_big, nmax, vmax, why.c_str());
   }
   ctx->tic("k_clean");
-  hipLaunchKernelGGL(k_clean, dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
+  hipLaunchKernelGGL(MA_GX_NAME(k_clean), dim3(ws.n_active), dim3(64), 0, ctx->stream, args);
   ctx->toc();
   MA_HIP(ctx, hipGetLastError());
+#ifdef MA_CLEAN_GX
+  MA_TRY_RC(run_graph_export(ctx, b, ws, *gx));
+#endif
   return MA_OK;
 }
 

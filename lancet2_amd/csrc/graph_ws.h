@@ -139,6 +139,19 @@ constexpr int kCgEdgeCap = 8;
 constexpr int kCgMaxCand = 15;
 constexpr int kCgHdr = 8 + 6 * 16;
 
+// ---- graph export (ma_assemble_graph_batch: clean.hip leaves marks, graph_export.hip writes the caller's arrays) ----
+// Mark record of an active slot, kGxMark words: [0] = rows | (route + 1) << 8, zero unless the window was reported by this
+// pass; then per row c of comp_* three words: the component id in nd_comp / cg_comp, its source node, its sink node.
+constexpr int kGxMark = 1 + 3 * 16;  // (max_comps <= 16: check_params)
+constexpr u32 kGxRouteSmall = 0, kGxRouteLarge = 1, kGxRouteHbm = 2, kGxRouteClean = 3;  // the slots of ma_last_graph_export
+struct GxDev {
+  ma_graph_out_t o;             // the caller's arrays (device pointers), addressed by GLOBAL window id
+  u32* mark;                    // [n_active][kGxMark]
+  unsigned long long* routes;   // [4] windows exported per route
+};
+int run_graph_export(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const GxDev& gx);  // graph_export.hip
+int run_graph_export_clear(ma_ctx* ctx, const GxDev& gx, const u32* win_status, int n, bool only_overflowed);
+
 // the k window w is built / cleaned with in the current pass
 __device__ __forceinline__ int win_kmer(GraphWs const& ws, int w) {
   u32 const k = ws.win_k[w];

@@ -62,6 +62,8 @@ struct KernelTimer {
   hipEvent_t beg, end;
 };
 
+struct GxDev;  // graph_ws.h: where a call that exports the graphs (ma_assemble_graph_batch) writes
+
 }  // namespace ma
 
 struct ma_ctx {
@@ -123,6 +125,11 @@ struct ma_ctx {
   int poa_retry = 0;
   ma::DevBuf poa_cause;
   unsigned long long poa_retry_counts[4] = {0, 0, 0, 0};
+  // ma_assemble_graph_batch: non-null while its assembly runs (clean.hip: run_clean_pass takes the marking kernels and
+  // launches k_graph_export; assemble.hip keeps to the rung-by-rung ladder); the marks of a pass's slots; the four route
+  // counters of ma_last_graph_export (device, read when asked for)
+  const ma::GxDev* gx = nullptr;
+  ma::DevBuf gx_mark, gx_routes;
   hipEvent_t sync_ev = nullptr;  // blocking-sync event: host threads sleep instead of spinning while the stream drains
   // host route (MA_MEM_HOST) of ma_process_batch, per lane: packed result records (pack.hip) and their pinned landing area
   ma::DevBuf pack_aux;

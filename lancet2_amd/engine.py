@@ -52,6 +52,9 @@ def load_library(path=None):
     if hasattr(lib, "ma_set_poa_retry"):  # (likewise: a build of before the POA retry passes)
         lib.ma_set_poa_retry.argtypes = capi.SET_POA_RETRY_ARGTYPES
         lib.ma_last_poa_retry.argtypes = capi.LAST_POA_RETRY_ARGTYPES
+    if hasattr(lib, "ma_assemble_graph_batch"):  # (likewise: a build of before the graph export)
+        lib.ma_assemble_graph_batch.argtypes = [C.c_void_p] * 4
+        lib.ma_last_graph_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     return lib
 
 
@@ -142,6 +145,30 @@ class Engine:
         o = capi.fill_struct(capi.AsmOut, out)
         self._check(self.lib.ma_assemble_batch(self.h, C.byref(b), C.byref(o)), "ma_assemble_batch")
         return out
+
+    def assemble_graph(self, arrs, n, nr, max_nodes=512, max_edges=2048, max_seq_bytes=32768):
+        """ma_assemble_graph_batch: assemble() + the pruned graph of every reported component (capi.graph_out_spec; the caps
+        are per window).  Returns (asm, graph); graph also carries the three caps under their names."""
+        out = self._alloc(capi.asm_out_spec(self.p, n))
+        gr = self._alloc(capi.graph_out_spec(self.p, n, max_nodes, max_edges, max_seq_bytes))
+        b = capi.make_batch_struct(arrs, n, nr)
+        self.assemble_graph_device(b, capi.fill_struct(capi.AsmOut, out), capi.make_graph_struct(gr, max_nodes, max_edges, max_seq_bytes))
+        gr.update(max_nodes=int(max_nodes), max_edges=int(max_edges), max_seq_bytes=int(max_seq_bytes))
+        return out, gr
+
+    def assemble_graph_device(self, batch_struct, asm, graph):
+        """ma_assemble_graph_batch on caller-made structs (either memory space); graph=None: a null pointer, the plain call"""
+        self._check(self.lib.ma_assemble_graph_batch(self.h, C.byref(batch_struct), C.byref(asm),
+                                                     C.byref(graph) if graph is not None else None), "ma_assemble_graph_batch")
+
+    def last_graph_export(self):
+        """Windows exported by the last assemble_graph(), per clean route (include/microasm.h: ma_last_graph_export).  A window
+        flagged MA_G_* is not counted; one that a capacity retry pass assembled again counts once per pass that wrote its rows."""
+        buf = (C.c_ulonglong * 4)()
+        n = self.lib.ma_last_graph_export(self.h, buf, 4)
+        if n < 0:
+            raise EngineError(f"ma_last_graph_export failed ({n}): {self.lib.ma_last_error(self.h).decode()}")
+        return {k: int(buf[i]) for i, k in enumerate(capi.GRAPH_EXPORT_KEYS) if i < n}
 
     def msa(self, arrs, n, nr, asm):
         out = self._alloc(capi.var_out_spec(self.p, n))

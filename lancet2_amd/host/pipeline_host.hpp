@@ -1727,4 +1727,116 @@ inline std::vector<VariantRecord> RecordsOfBatch(const ma_params_t& p, FlatBatch
   return out;
 }
 
+// ---- graph snapshots: one DOT digraph per exported component (ma_assemble_graph_batch) --------------------------------------
+// What the reference buffers per component with --out-graphs-tgz (cbdg/graph.cpp:216-223), drawn from the export's arrays and
+// the assembly rows of the same call.  Per node: the stored sequence, its reverse complement, `slot:sign`, length and total
+// read support; the component's two anchors are boxes.  Per stored edge: the signs on its tail and head side.  The edges of
+// every haplotype's walk carry that haplotype's colour (walk 0 = REF); an edge on several walks carries all of them.  A walk
+// is found from the row's bases alone: the walk from the source anchor that spells them, the first node whole and every next
+// one minus its first k - 1 bases, a node read as stored when the edge's sign on its side is +, reverse complemented
+// otherwise, every edge leaving on the sign the walk arrived with (max_flow.cpp:64-113).
+namespace dot_detail {
+inline std::string RevCompAscii(std::string_view s) {
+  std::string out(s.size(), 'N');
+  for (size_t i = 0; i < s.size(); ++i) {
+    char const c = s[s.size() - 1 - i];
+    out[i] = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c == 'a' ? 't' : c == 'c' ? 'g' : c == 'g' ? 'c' : c == 't' ? 'a' : (c == 'n' ? 'n' : 'N');
+  }
+  return out;
+}
+struct DotEdge {
+  uint32_t src, dst, kind;
+  std::vector<uint32_t> walks;  // haplotypes whose walk crosses it
+};
+}  // namespace dot_detail
+
+inline constexpr const char* kDotWalkColours[8] = {"royalblue3", "firebrick2", "darkorange2", "seagreen4", "orchid3", "goldenrod3", "turquoise4", "sienna"};
+
+// w: window index in the batch; comp: component slot (< win_ncomp[w]); k: win_k[w]; title: the graph's name.  Returns the empty
+// string when the window's export is flagged (ma_gstatus) or holds no node of the component.
+inline std::string RenderComponentDot(const ma_params_t& p, const ma_asm_out_t& a, const ma_graph_out_t& g, int w, uint32_t comp, uint32_t k,
+                                      std::string const& title) {
+  using dot_detail::DotEdge;
+  size_t const W = static_cast<size_t>(w), MN = static_cast<size_t>(g.max_nodes), ME = static_cast<size_t>(g.max_edges),
+               MS = static_cast<size_t>(g.max_seq_bytes), S = static_cast<size_t>(p.num_samples);
+  if (g.win_gstatus[W] != 0) return {};
+  uint32_t const nn = g.win_nnodes[W], ne = g.win_nedges[W];
+  auto seq_of = [&](uint32_t s) {
+    return std::string_view(reinterpret_cast<const char*>(g.seq_pool) + W * MS + g.node_seq_off[W * MN + s], g.node_len[W * MN + s]);
+  };
+  std::vector<uint32_t> mine;
+  for (uint32_t s = 0; s < nn; ++s)
+    if (g.node_comp[W * MN + s] == comp) mine.push_back(s);
+  if (mine.empty()) return {};
+  std::vector<DotEdge> edges;
+  std::unordered_map<uint32_t, std::vector<size_t>> out_of;  // node slot -> its edges
+  uint32_t source = UINT32_MAX;
+  for (uint32_t e = 0; e < ne; ++e) {
+    uint32_t const src = g.edge_src[W * ME + e];
+    if (g.node_comp[W * MN + src] != comp) continue;
+    out_of[src].push_back(edges.size());
+    edges.push_back(DotEdge{src, g.edge_dst[W * ME + e], g.edge_kind[W * ME + e], {}});
+  }
+  for (uint32_t s : mine)
+    if (g.node_flags[W * MN + s] & 1u) source = s;
+  // the walk of every haplotype row of the component
+  size_t const ci = W * static_cast<size_t>(p.max_comps) + comp;
+  uint32_t const hap0 = a.comp_hap0[ci], nh = a.comp_nhaps[ci];
+  for (uint32_t h = 0; h < nh && source != UINT32_MAX; ++h) {
+    size_t const hi = W * static_cast<size_t>(p.max_haps) + hap0 + h;
+    std::string_view const target(reinterpret_cast<const char*>(a.hap_bases) + hi * static_cast<size_t>(p.max_hap_len), a.hap_len[hi]);
+    std::vector<size_t> walk, found;
+    std::function<bool(uint32_t, uint32_t, size_t)> go = [&](uint32_t node, uint32_t sign, size_t pos) -> bool {
+      if (pos == target.size() && (g.node_flags[W * MN + node] & 2u) && !walk.empty()) {
+        found = walk;
+        return true;
+      }
+      for (size_t ei : out_of[node]) {
+        DotEdge const& e = edges[ei];
+        if (((e.kind >> 1) & 1u) != sign) continue;
+        std::string_view const ds = seq_of(e.dst);
+        if (ds.size() + 1 < k) continue;  // (a node is never shorter than k)
+        std::string const piece = (e.kind & 1u) ? dot_detail::RevCompAscii(ds).substr(k - 1) : std::string(ds.substr(k - 1));
+        if (pos + piece.size() > target.size() || target.compare(pos, piece.size(), piece) != 0) continue;
+        walk.push_back(ei);
+        if (go(e.dst, e.kind & 1u, pos + piece.size())) return true;
+        walk.pop_back();
+      }
+      return false;
+    };
+    for (uint32_t sign = 0; sign < 2 && found.empty(); ++sign) {
+      std::string const first = sign ? dot_detail::RevCompAscii(seq_of(source)) : std::string(seq_of(source));
+      if (target.size() >= first.size() && target.compare(0, first.size(), first) == 0) go(source, sign, first.size());
+    }
+    for (size_t ei : found) edges[ei].walks.push_back(h);
+  }
+  std::ostringstream os;
+  os << "digraph \"" << title << "\" {\n  rankdir=LR;\n  node [fontname=\"monospace\", fontsize=9];\n";
+  for (uint32_t s : mine) {
+    size_t const i = W * MN + s;
+    unsigned long long cov = 0;
+    for (size_t x = 0; x < S; ++x) cov += g.node_cnt[i * S + x];
+    std::string_view const sq = seq_of(s);
+    uint8_t const fl = g.node_flags[i];
+    os << "  n" << s << " [label=\"" << sq << "\\n" << dot_detail::RevCompAscii(sq) << "\\n" << s << ":" << (g.node_sign[i] ? '+' : '-')
+       << " len=" << sq.size() << " cov=" << cov << "\"";
+    if (fl & 1u) os << ", shape=box, style=filled, fillcolor=palegreen, xlabel=\"source\"";
+    else if (fl & 2u) os << ", shape=box, style=filled, fillcolor=lightsalmon, xlabel=\"sink\"";
+    else if (g.node_label[i] & 1u) os << ", style=filled, fillcolor=gray90";
+    os << "];\n";
+  }
+  for (auto const& e : edges) {
+    os << "  n" << e.src << " -> n" << e.dst << " [taillabel=\"" << (((e.kind >> 1) & 1u) ? '-' : '+') << "\", headlabel=\""
+       << ((e.kind & 1u) ? '-' : '+') << "\"";
+    if (!e.walks.empty()) {
+      os << ", penwidth=2, color=\"";
+      for (size_t x = 0; x < e.walks.size(); ++x) os << (x ? ":" : "") << kDotWalkColours[e.walks[x] % 8];
+      os << "\"";
+    }
+    os << "];\n";
+  }
+  os << "}\n";
+  return os.str();
+}
+
 }  // namespace lancet2_amd::host
