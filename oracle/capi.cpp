@@ -598,9 +598,12 @@ int orc_annotate_batch(const ma_params_t* prm, const ma_batch_t* b, const ma_asm
       o->seq_cx_d[vi * 3 + 2] = s.delta_flank_lq;
       // cbdg/graph_complexity.h:160-166 + variant_annotator.cpp:87-99
       usize const ci = static_cast<usize>(w) * MC + c;
-      f64 const cc = static_cast<f64>(a->comp_cx[ci * 3 + 0]), bp = static_cast<f64>(a->comp_cx[ci * 3 + 1]);
-      f64 const raw = (cc * bp * a->comp_cxf[ci * 4 + 1]) / (a->comp_cxf[ci * 4 + 0] + 1e-6);
-      o->graph_cx[vi * 3 + 0] = std::log10(1.0 + raw);
+      GraphComplexity gc;
+      gc.cyclomatic = a->comp_cx[ci * 3 + 0];
+      gc.branch_points = a->comp_cx[ci * 3 + 1];
+      gc.unitig_ratio = a->comp_cxf[ci * 4 + 0];
+      gc.coverage_cv = a->comp_cxf[ci * 4 + 1];
+      o->graph_cx[vi * 3 + 0] = gc.GraphEntanglementIndex();
       o->graph_cx[vi * 3 + 1] = a->comp_cxf[ci * 4 + 2];
       o->graph_cx[vi * 3 + 2] = static_cast<f64>(a->comp_cx[ci * 3 + 2]);
     }

@@ -824,6 +824,25 @@ int orc_kmer_merge_chain(const char* seq, uint64_t n, uint64_t k, int reverse, c
   return static_cast<int>(merged.size());
 }
 
+// tests/cbdg/graph_complexity_test.cpp:18-44: a GraphComplexity as its default constructor leaves it (vals == NULL) or with
+// vals = {cyclomatic, branch points, coverage CV, unitig ratio}.  out_i: cyclomatic, branch points, the two thresholds;
+// *out_gei: GraphEntanglementIndex().  Returns IsComplex().
+int orc_graph_complexity_kat(const double* vals, uint64_t* out_i, double* out_gei) {
+  orc::GraphComplexity gc;
+  if (vals != nullptr) {
+    gc.cyclomatic = static_cast<orc::u64>(vals[0]);
+    gc.branch_points = static_cast<orc::u64>(vals[1]);
+    gc.coverage_cv = vals[2];
+    gc.unitig_ratio = vals[3];
+  }
+  out_i[0] = gc.cyclomatic;
+  out_i[1] = gc.branch_points;
+  out_i[2] = orc::GraphComplexity::MAX_CYCLOMATIC_COMPLEXITY;
+  out_i[3] = orc::GraphComplexity::MAX_BRANCH_POINTS;
+  *out_gei = gc.GraphEntanglementIndex();
+  return gc.IsComplex() ? 1 : 0;
+}
+
 // Node::Confidence (node.cpp:59-79)
 uint32_t orc_confidence(const uint32_t* counts, int n, int num_samples, int is_ref) {
   orc::Node nd;

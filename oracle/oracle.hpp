@@ -35,7 +35,12 @@ struct Params {
 struct GraphComplexity {
   u64 cyclomatic = 0, branch_points = 0, max_dir_degree = 0;
   f64 unitig_ratio = 0.0, coverage_cv = 0.0, tip_to_path = 0.0;
-  bool IsComplex() const { return cyclomatic >= 50 && branch_points >= 50; }  // :112-121
+  static constexpr u64 MAX_CYCLOMATIC_COMPLEXITY = 50, MAX_BRANCH_POINTS = 50;  // :112-113
+  bool IsComplex() const { return cyclomatic >= MAX_CYCLOMATIC_COMPLEXITY && branch_points >= MAX_BRANCH_POINTS; }  // :118-121
+  f64 GraphEntanglementIndex() const {  // :160-166
+    f64 const raw = (static_cast<f64>(cyclomatic) * static_cast<f64>(branch_points) * coverage_cv) / (unitig_ratio + 1e-6);
+    return std::log10(1.0 + raw);
+  }
 };
 
 // cbdg/path.h:19-85 -- assembled haplotype.

@@ -444,6 +444,37 @@ def test_graph_complexity_chain_and_single_bubble():
         assert a["comp_nhaps"].reshape(n, p.max_comps)[:, 0].tolist() == [1 + n_somatic] * 3
 
 
+def test_graph_complexity_defaults_and_thresholds():
+    """tests/cbdg/graph_complexity_test.cpp:18-44: a default-constructed GraphComplexity is not complex, with cyclomatic
+    complexity 0 and no branch point; the gate's thresholds are 50 and 50 (both must be reached: graph_complexity.h:118-121);
+    the default Graph Entanglement Index is 0 within 1e-10.  tests/graph_export_ref.py has no default state and no gate, only
+    the computed function (graph_complexity.cpp:16-93): on a component without nodes that leaves every field at its default but
+    the cyclomatic complexity -- 0 edges >= 0 nodes gives 0 - 0 + 1 (:73) -- and the index over its fields is the default 0."""
+    import ctypes as C
+    import math
+    import graph_export_ref
+    lib = oracle()
+    lib.orc_graph_complexity_kat.restype = C.c_int
+
+    def kat(vals):
+        out_i, gei = (C.c_uint64 * 4)(), C.c_double()
+        arg = (C.c_double * 4)(*vals) if vals is not None else None
+        return lib.orc_graph_complexity_kat(arg, out_i, C.byref(gei)), list(out_i), gei.value
+
+    complex_, ints, gei = kat(None)
+    assert complex_ == 0 and ints[0] == 0 and ints[1] == 0
+    assert ints[2] == 50 and ints[3] == 50
+    assert abs(gei) <= 1e-10
+    # the thresholds as IsComplex applies them: >= on both, AND
+    assert [kat((cc, bp, 0.0, 0.0))[0] for cc, bp in ((50, 50), (49, 50), (50, 49), (487, 0), (0, 1127), (51, 51))] == [1, 0, 0, 0, 0, 1]
+    # and the index itself where it is not 0: log10(1 + CC x BP x CV / (UR + 1e-6)), graph_complexity.h:160-166
+    assert kat((3, 6, 0.5, 0.8))[2] == math.log10(1.0 + (3.0 * 6.0 * 0.5) / (0.8 + 1e-6))
+    cx = graph_export_ref.complexity([])
+    assert (cx["cyclomatic"], cx["branch_points"], cx["max_dir_degree"]) == (1, 0, 0)
+    assert (cx["unitig_ratio"], cx["coverage_cv"], cx["tip_to_path"]) == (0.0, 0.0, 0.0)
+    assert math.log10(1.0 + (cx["cyclomatic"] * cx["branch_points"] * cx["coverage_cv"]) / (cx["unitig_ratio"] + 1e-6)) == 0.0
+
+
 def test_genotype_pls_against_scipy():
     """caller/genotype_likelihood.cpp:93-272 -- the oracle's Dirichlet-multinomial PLs equal an independent scipy
     evaluation of ln P(c | alpha) = lnG(sum a) - lnG(N + sum a) + sum [lnG(c_i + a_i) - lnG(a_i)] with
