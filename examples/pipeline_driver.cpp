@@ -10,6 +10,8 @@
 //             (--read-meta with --out-vcf: ma_prefetch_meta_batch, and that call with the reads' MAPQ, clip and pair flags,
 //              insert size and start -- RMQ, SCA, FLD, RPCD, MQCD, FSSE are printed too: 24 of 24 FORMAT values)
 //             (--out-graphs-dir DIR: debugging -- the batch once more through ma_assemble_graph_batch, one DOT file per component)
+//             (--out-msa-dir DIR: debugging -- the batch once more through ma_assemble_batch + ma_msa_graph_batch, a GFA and a
+//              FASTA file per component)
 //   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
 // Build (no HIP headers needed; zlib only for BAM input):
@@ -243,6 +245,75 @@ long WriteGraphs(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& ref, Fl
   return written;
 }
 
+// --out-msa-dir: the batch once more through ma_assemble_batch + ma_msa_graph_batch; per component of every assembled window
+// msa__<chrom>_<start>_<end>__c<comp>.gfa (the SPOA graph) and .fasta (the MSA rows), as the reference names and prints them
+// with --out-graphs-tgz.  Windows that come back flagged (MA_P_*) are re-submitted once -- the batch again, with the largest
+// reported needs as caps.  Returns the number of files written, -1 when a call failed.
+struct PoaArrays {
+  std::vector<uint32_t> u32;
+  std::vector<uint8_t> u8;
+  ma_poa_out_t x{};
+  void Allocate(const ma_params_t& p, int n, int32_t mn, int32_t me, int32_t mx) {
+    size_t const N = n, MC = p.max_comps, MH = p.max_haps, MN = mn, ME = me, MX = mx;
+    u32.assign(4 * N + 5 * N * MC + 3 * N * MN + 3 * N * ME + N * MH, 0);
+    u8.assign(N * MN + N * MH * MX, 0);
+    uint32_t* u = u32.data();
+    uint8_t* b = u8.data();
+    auto tu = [&](size_t c) { uint32_t* r = u; u += c; return r; };
+    auto tb = [&](size_t c) { uint8_t* r = b; b += c; return r; };
+    x.max_pnodes = mn; x.max_pedges = me; x.max_cols = mx;
+    x.win_pstatus = tu(N); x.win_npnodes = tu(N); x.win_npedges = tu(N); x.win_ncols = tu(N);
+    x.comp_pnode0 = tu(N * MC); x.comp_npnodes = tu(N * MC); x.comp_pedge0 = tu(N * MC); x.comp_npedges = tu(N * MC);
+    x.comp_ncols = tu(N * MC);
+    x.pnode_base = tb(N * MN); x.pnode_rank = tu(N * MN); x.pnode_col = tu(N * MN); x.pnode_haps = tu(N * MN);
+    x.pedge_tail = tu(N * ME); x.pedge_head = tu(N * ME); x.pedge_haps = tu(N * ME);
+    x.hap_first = tu(N * MH); x.msa = tb(N * MH * MX);
+  }
+};
+
+long WriteMsaFiles(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& ref, FlatBatch const& fb, std::string const& dir) {
+  int const n = fb.view.n_windows;
+  Outputs o;
+  PoaArrays pa;
+  int32_t caps[3] = {2048, 4096, 2048};
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    o.Allocate(prm, n, false);
+    pa.Allocate(prm, n, caps[0], caps[1], caps[2]);
+    if (ma_assemble_batch(ctx, &fb.view, &o.asmb) != MA_OK) return -1;
+    if (ma_msa_graph_batch(ctx, &fb.view, &o.asmb, &o.vars, &pa.x) != MA_OK) return -1;
+    bool flagged = false;
+    for (int w = 0; w < n; ++w) {
+      flagged = flagged || pa.x.win_pstatus[w] != 0;
+      caps[0] = std::max<int32_t>(caps[0], static_cast<int32_t>(pa.x.win_npnodes[w]));
+      caps[1] = std::max<int32_t>(caps[1], static_cast<int32_t>(pa.x.win_npedges[w]));
+      caps[2] = std::max<int32_t>(caps[2], static_cast<int32_t>(pa.x.win_ncols[w]));
+    }
+    if (!flagged) break;
+  }
+  long written = 0;
+  for (int w = 0; w < n; ++w) {
+    auto const& win = fb.windows[static_cast<size_t>(w)];
+    for (uint32_t c = 0; c < o.asmb.win_ncomp[w]; ++c) {
+      std::string const name = "msa__" + ref.chroms[static_cast<size_t>(win.chrom)].name + "_" + std::to_string(win.start1) + "_" +
+                               std::to_string(win.end1) + "__c" + std::to_string(c);
+      std::string const texts[2] = {RenderComponentGfa(prm, o.asmb, pa.x, w, c), RenderComponentFasta(prm, o.asmb, pa.x, w, c)};
+      if (texts[0].empty()) {  // a window the POA stage left out or capped, or one still flagged after the re-submission
+        std::fprintf(stderr, "pipeline_driver: --out-msa-dir: no MSA for %s (window status %u, export status %u: needs %u nodes, %u edges, %u columns)\n",
+                     name.c_str(), o.asmb.win_status[w], pa.x.win_pstatus[w], pa.x.win_npnodes[w], pa.x.win_npedges[w], pa.x.win_ncols[w]);
+        continue;
+      }
+      for (int k = 0; k < 2; ++k) {
+        FILE* f = std::fopen((dir + "/" + name + (k ? ".fasta" : ".gfa")).c_str(), "w");
+        if (!f) { std::perror("--out-msa-dir"); return -1; }
+        std::fputs(texts[k].c_str(), f);
+        std::fclose(f);
+        ++written;
+      }
+    }
+  }
+  return written;
+}
+
 AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed) {
   bool const bam = path.size() > 4 && path.substr(path.size() - 4) == ".bam";
 #ifdef LANCET2_AMD_WITH_ZLIB
@@ -272,7 +343,7 @@ int main(int argc, char** argv) {
   //  in force -- ADVICE r5; the flat arrays are far below 32 MiB)
   if (mallopt(M_MMAP_THRESHOLD, 32 << 20) != 1 || mallopt(M_TRIM_THRESHOLD, 1 << 30) != 1 || mallopt(M_TOP_PAD, 64 << 20) != 1)
     std::fprintf(stderr, "pipeline_driver: mallopt rejected a setting; large arrays fall back to mmap (slower, still correct)\n");
-  std::string ref_path, out_path, dump_dir, vcf_path, command_line, graphs_dir;
+  std::string ref_path, out_path, dump_dir, vcf_path, command_line, graphs_dir, msa_dir;
   for (int i = 0; i < argc; ++i) command_line += std::string(i ? " " : "") + argv[i];
   double gc_frac = 0.41;  // --genome-gc-bias of the reference CLI: background GC of the LongdustQ null model
   std::vector<std::string> normals, tumors, regions;
@@ -310,6 +381,7 @@ int main(int argc, char** argv) {
     else if (a == "--extract-threads") extract_threads = std::max(1, std::atoi(next()));  // (the reference: -T, one collector per worker)
     else if (a == "--dump") dump_dir = next();
     else if (a == "--out-graphs-dir") graphs_dir = next();  // debugging: one DOT file per assembled component (assembles twice)
+    else if (a == "--out-msa-dir") msa_dir = next();  // debugging: a GFA and a FASTA file per component (assembles and aligns twice)
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
     else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
@@ -328,6 +400,10 @@ int main(int argc, char** argv) {
                          "                  component a window reported -- the pruned graph its haplotypes were walked on.  Not with --packed-reads.\n"
                          "                  Costs 62 KB of host memory per window of a batch (and as much on the device), more when windows\n"
                          "                  outgrow the first caps and the batch is re-submitted: keep --batch-windows at a few hundred\n"
+                         "  --out-msa-dir DIR  a debugging mode that ASSEMBLES AND ALIGNS EVERY BATCH TWICE: after a batch's chained call the batch\n"
+                         "                  goes through ma_assemble_batch + ma_msa_graph_batch and DIR/msa__<chrom>_<start>_<end>__c<comp>.gfa\n"
+                         "                  (the SPOA graph: a segment per node, a link per edge, a path per haplotype) and .fasta (the MSA\n"
+                         "                  rows) are written for every component.  Not with --packed-reads; keep --batch-windows at a few hundred\n"
                          "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
                          "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
                          "                  all 24 FORMAT values.  Without it those six are \".\"\n"
@@ -341,6 +417,10 @@ int main(int argc, char** argv) {
   }
   if (packed_reads && !graphs_dir.empty()) {  // (the stage calls do not take the packed form: include/microasm.h)
     std::fprintf(stderr, "pipeline_driver: --out-graphs-dir needs ASCII reads (not with --packed-reads)\n");
+    return 2;
+  }
+  if (packed_reads && !msa_dir.empty()) {  // (likewise)
+    std::fprintf(stderr, "pipeline_driver: --out-msa-dir needs ASCII reads (not with --packed-reads)\n");
     return 2;
   }
   rp.packed_reads = packed_reads;
@@ -623,7 +703,7 @@ int main(int argc, char** argv) {
   });
   // ---- stage 2: engine ----
   bool const with_meta = read_meta && !vcf_path.empty();
-  size_t n_graph_files = 0;
+  size_t n_graph_files = 0, n_msa_files = 0;
   std::thread engine([&] {
     Job j;
     while (to_engine.Pop(&j)) {
@@ -658,6 +738,15 @@ int main(int argc, char** argv) {
           j.err = std::string("--out-graphs-dir: ") + ma_last_error(ctx);
         } else {
           n_graph_files += static_cast<size_t>(nf);
+        }
+      }
+      if (j.rc == MA_OK && !msa_dir.empty()) {
+        long const nf = WriteMsaFiles(ctx, prm, ref, *j.batch, msa_dir);
+        if (nf < 0) {
+          j.rc = MA_ERR_HIP;
+          j.err = std::string("--out-msa-dir: ") + ma_last_error(ctx);
+        } else {
+          n_msa_files += static_cast<size_t>(nf);
         }
       }
       busy_engine += secs(Clock::now() - t0);
@@ -735,6 +824,7 @@ int main(int argc, char** argv) {
                "%zu with a capacity flag, %zu records\n",
                windows.size(), n_skipped[1], n_skipped[2], n_skipped[3], n_skipped[4], n_assembled, n_flagged, n_records);
   if (!graphs_dir.empty()) std::fprintf(stderr, "pipeline_driver: %zu component graphs written to %s\n", n_graph_files, graphs_dir.c_str());
+  if (!msa_dir.empty()) std::fprintf(stderr, "pipeline_driver: %zu MSA files written to %s\n", n_msa_files, msa_dir.c_str());
   double const wall = secs(Clock::now() - t_start);
   size_t blocks = 0;
   bool any_indexed = false;

@@ -461,6 +461,54 @@ int ma_assemble_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out
  * Returns the number of entries written. */
 int ma_last_graph_export(ma_ctx_t* ctx, unsigned long long* out, int cap);
 
+/* ---- POA export: the SPOA graph and the MSA rows of every component --------------------------------------------------- */
+/* What the reference writes per component with --out-graphs-tgz beside the DOT file (core/variant_builder.cpp:47-70,
+ * caller/msa_builder.cpp:44-102): msa__<region>__c<i>.gfa -- one segment per POA node, one link per edge, one path per
+ * haplotype -- and msa__<region>__c<i>.fasta, the rows of spoa::Graph::GenerateMultipleSequenceAlignment.  Exported is the
+ * graph the variants of ma_var_out_t were read from: after the component's last haplotype, in the state the bubble walk sees.
+ * The counts always hold the NEED.  If a need exceeds its cap the window gets the matching ma_pstatus bit and none of its
+ * rows is defined; a write never passes a cap; re-submit with the reported need.  All counts and win_pstatus are 0 for the
+ * windows the stage skips (win_ncomp == 0, MA_W_NO_HAPLOTYPE, MA_W_LEN_OVERFLOW).  For a window this call leaves
+ * MA_W_VAR_OVERFLOW the export only promises to stay inside the caps.  With ma_set_poa_retry a retried window's rows are
+ * those of the retry pass that called it (its first pass's counts are cleared first).  A component that holds an empty
+ * haplotype is undefined (SPOA gives an empty sequence no label).  NOT exported: edge weights (the engine does not keep
+ * them, the GFA does not print them) and SPOA's consensus.  win_status is never touched by the export. */
+enum ma_pstatus { MA_P_NODE_OVERFLOW = 1u << 0, MA_P_EDGE_OVERFLOW = 1u << 1, MA_P_COL_OVERFLOW = 1u << 2 };
+typedef struct ma_poa_out {
+  int32_t max_pnodes, max_pedges;  /* caller's caps per window, summed over the window's components */
+  int32_t max_cols;                /* cap per component: MSA columns; also the stride of one haplotype's row */
+  uint32_t* win_pstatus;           /* [n] ma_pstatus */
+  uint32_t* win_npnodes;           /* [n] the NEED, also beyond the cap */
+  uint32_t* win_npedges;           /* [n] likewise */
+  uint32_t* win_ncols;             /* [n] likewise: the most columns of any component */
+  /* per component, [n * max_comps] */
+  uint32_t *comp_pnode0, *comp_npnodes, *comp_pedge0, *comp_npedges, *comp_ncols;
+  /* per POA node, stride max_pnodes.  A component's nodes are contiguous from comp_pnode0, in spoa's id order:
+     Node::id = slot - comp_pnode0 */
+  uint8_t*  pnode_base;            /* decoder(code): the ASCII letter */
+  uint32_t* pnode_rank;            /* index in Graph::rank_to_node() */
+  uint32_t* pnode_col;             /* MSA column */
+  uint32_t* pnode_haps;            /* bit h: the path of the component's h-th haplotype (0 = REF) holds the node */
+  /* per out-edge, stride max_pedges.  A node's out-edges are contiguous in Node::outedges order, nodes in id order,
+     components in order from comp_pedge0 */
+  uint32_t *pedge_tail, *pedge_head;  /* component-local ids */
+  uint32_t* pedge_haps;               /* Edge::labels as a mask */
+  /* per haplotype slot, [n * max_haps] */
+  uint32_t* hap_first;             /* Graph::sequences()[h]: component-local id of the path's first node */
+  uint8_t*  msa;                   /* [n * max_haps * max_cols]: row of slot comp_hap0 + h, comp_ncols bytes, '-' = gap */
+} ma_poa_out_t;
+/* ma_msa_batch + the export.  px == NULL IS ma_msa_batch: the same kernels, nothing allocated.  Otherwise every array of px
+ * is required (MA_ERR_ARG) and every cap must be >= 1 (MA_ERR_PARAM).  Both memory spaces: with MA_MEM_DEVICE the arrays of
+ * px are device pointers (the struct itself is always in host memory).  The ma_var_out_t arrays and win_status are byte for
+ * byte those of ma_msa_batch on the same input.  An exporting call runs every pass as host-counted rounds (what
+ * MA_POA_SCHED=0 selects) with kernels of its own; single lane, like every stage call. */
+int ma_msa_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* out, const ma_poa_out_t* px);
+/* Windows the last ma_msa_graph_batch ran to their end with the export, per kind of pass:
+ *   out[0] first pass (16-bit labels)   out[1] LAB32 pass   out[2] width retry   out[3] capacity retry
+ * A retried window counts in its first pass and in its retry pass.  All zero after a call with px == NULL.
+ * Returns the number of entries written. */
+int ma_last_poa_export(ma_ctx_t* ctx, unsigned long long* out, int cap);
+
 /* Work counters accumulated over the same region as ma_last_kernel_times (reset by ma_timing_control):
  *   out[0] read x haplotype pairs seen by ma_genotype_batch      out[1] pairs that needed the DP
  *   out[2] windows passed to ma_assemble_batch                   out[3] k attempts x windows assembled

@@ -209,6 +209,37 @@ def make_graph_struct(arrays, max_nodes, max_edges, max_seq_bytes):
     return s
 
 
+MA_P_NODE_OVERFLOW, MA_P_EDGE_OVERFLOW, MA_P_COL_OVERFLOW = 1, 2, 4
+POA_EXPORT_KEYS = ("first", "lab32", "retry_width", "retry_capacity")  # ma_last_poa_export: windows exported per kind of pass
+POA_OUT_CAPS = ("max_pnodes", "max_pedges", "max_cols")
+
+
+class PoaOut(C.Structure):
+    """ma_poa_out_t: the three caps, then eighteen arrays -- all required"""
+    _fields_ = [(n, C.c_int32) for n in POA_OUT_CAPS] + [(n, C.c_void_p) for n in (
+        "win_pstatus", "win_npnodes", "win_npedges", "win_ncols", "comp_pnode0", "comp_npnodes", "comp_pedge0", "comp_npedges",
+        "comp_ncols", "pnode_base", "pnode_rank", "pnode_col", "pnode_haps", "pedge_tail", "pedge_head", "pedge_haps",
+        "hap_first", "msa")]
+
+
+def poa_out_spec(p, n, max_pnodes, max_pedges, max_cols):
+    """arrays of ma_poa_out_t for n windows: max_pnodes / max_pedges per window, max_cols per component (ma_msa_graph_batch)"""
+    MC, MH, MN, ME, MX = p.max_comps, p.max_haps, max_pnodes, max_pedges, max_cols
+    return dict(win_pstatus=(np.uint32, n), win_npnodes=(np.uint32, n), win_npedges=(np.uint32, n), win_ncols=(np.uint32, n),
+                comp_pnode0=(np.uint32, n * MC), comp_npnodes=(np.uint32, n * MC), comp_pedge0=(np.uint32, n * MC),
+                comp_npedges=(np.uint32, n * MC), comp_ncols=(np.uint32, n * MC), pnode_base=(np.uint8, n * MN),
+                pnode_rank=(np.uint32, n * MN), pnode_col=(np.uint32, n * MN), pnode_haps=(np.uint32, n * MN),
+                pedge_tail=(np.uint32, n * ME), pedge_head=(np.uint32, n * ME), pedge_haps=(np.uint32, n * ME),
+                hap_first=(np.uint32, n * MH), msa=(np.uint8, n * MH * MX))
+
+
+def make_poa_struct(arrays, max_pnodes, max_pedges, max_cols):
+    """ma_poa_out_t over a dict of arrays (numpy, torch tensors or raw pointers; kept alive by the caller)"""
+    s = fill_struct(PoaOut, {k: v for k, v in arrays.items() if k not in POA_OUT_CAPS})
+    s.max_pnodes, s.max_pedges, s.max_cols = int(max_pnodes), int(max_pedges), int(max_cols)
+    return s
+
+
 def gate_out_spec(n):
     return dict(max_approx=(np.uint32, n), max_exact=(np.uint32, n))
 

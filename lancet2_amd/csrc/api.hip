@@ -114,6 +114,19 @@ std::vector<OutField> graph_fields(const ma_params_t& p, int n, const ma_graph_o
           {off_of(&ma_graph_out_t::seq_pool), N * MS}};
 }
 
+std::vector<OutField> poa_fields(const ma_params_t& p, int n, const ma_poa_out_t& x) {
+  size_t const N = n, MC = p.max_comps, MH = p.max_haps, MN = x.max_pnodes, ME = x.max_pedges, MX = x.max_cols;
+  return {{off_of(&ma_poa_out_t::win_pstatus), 4 * N}, {off_of(&ma_poa_out_t::win_npnodes), 4 * N},
+          {off_of(&ma_poa_out_t::win_npedges), 4 * N}, {off_of(&ma_poa_out_t::win_ncols), 4 * N},
+          {off_of(&ma_poa_out_t::comp_pnode0), 4 * N * MC}, {off_of(&ma_poa_out_t::comp_npnodes), 4 * N * MC},
+          {off_of(&ma_poa_out_t::comp_pedge0), 4 * N * MC}, {off_of(&ma_poa_out_t::comp_npedges), 4 * N * MC},
+          {off_of(&ma_poa_out_t::comp_ncols), 4 * N * MC}, {off_of(&ma_poa_out_t::pnode_base), N * MN},
+          {off_of(&ma_poa_out_t::pnode_rank), 4 * N * MN}, {off_of(&ma_poa_out_t::pnode_col), 4 * N * MN},
+          {off_of(&ma_poa_out_t::pnode_haps), 4 * N * MN}, {off_of(&ma_poa_out_t::pedge_tail), 4 * N * ME},
+          {off_of(&ma_poa_out_t::pedge_head), 4 * N * ME}, {off_of(&ma_poa_out_t::pedge_haps), 4 * N * ME},
+          {off_of(&ma_poa_out_t::hap_first), 4 * N * MH}, {off_of(&ma_poa_out_t::msa), N * MH * MX}};
+}
+
 void*& ptr_at(void* strct, size_t off) { return *reinterpret_cast<void**>(static_cast<char*>(strct) + off); }
 void* ptr_at(const void* strct, size_t off) {
   return *reinterpret_cast<void* const*>(static_cast<const char*>(strct) + off);
@@ -1314,7 +1327,7 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->pack_aux.release();
   ctx->ws_unpack.release();
   ctx->ws_sort.release();
-  ctx->gx_mark.release(); ctx->gx_routes.release();
+  ctx->gx_mark.release(); ctx->gx_routes.release(); ctx->px_ctr.release();
   ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
@@ -1574,6 +1587,59 @@ int ma_msa_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, c
     MA_HIP(ctx, ma_stream_sync(ctx));
   }
   return MA_OK;
+}
+
+int ma_msa_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* asmb, const ma_var_out_t* out, const ma_poa_out_t* px) {
+  if (!px) {  // the plain call: the same kernels, nothing allocated
+    if (ctx) for (auto& c : ctx->poa_export_counts) c = 0;
+    return ma_msa_batch(ctx, b, asmb, out);
+  }
+  MA_BEGIN(ctx);
+  if (!out || !asmb) return MA_ERR_ARG;
+  if (!px->win_pstatus || !px->win_npnodes || !px->win_npedges || !px->win_ncols || !px->comp_pnode0 || !px->comp_npnodes ||
+      !px->comp_pedge0 || !px->comp_npedges || !px->comp_ncols || !px->pnode_base || !px->pnode_rank || !px->pnode_col ||
+      !px->pnode_haps || !px->pedge_tail || !px->pedge_head || !px->pedge_haps || !px->hap_first || !px->msa)
+    return MA_ERR_ARG;
+  if (px->max_pnodes < 1 || px->max_pedges < 1 || px->max_cols < 1) return MA_ERR_PARAM;
+  for (auto& c : ctx->poa_export_counts) c = 0;
+  DBatch d;
+  MA_TRY(stage_batch(ctx, b, &d));
+  OutMirror<ma_asm_out_t> a;
+  MA_TRY(a.prepare(ctx, asmb, asm_fields(ctx->prm, d.n_windows), 2, true));
+  OutMirror<ma_var_out_t> v;
+  MA_TRY(v.prepare(ctx, out, var_fields(ctx->prm, d.n_windows), 16, false));
+  OutMirror<ma_poa_out_t> x;
+  std::vector<OutField> const xf = poa_fields(ctx->prm, d.n_windows, *px);
+  MA_TRY(x.prepare(ctx, px, xf, 72, false));
+  x.dev.max_pnodes = px->max_pnodes;
+  x.dev.max_pedges = px->max_pedges;
+  x.dev.max_cols = px->max_cols;
+  // every window starts with nothing exported: the four per-window and the five per-component count arrays
+  for (size_t i = 0; i < 9; ++i)
+    if (xf[i].bytes) MA_HIP(ctx, hipMemsetAsync(ptr_at(&x.dev, xf[i].offset), 0, xf[i].bytes, ctx->stream));
+  MA_HIP(ctx, ctx->px_ctr.reserve(4 * sizeof(u32)));
+  MA_HIP(ctx, hipMemsetAsync(ctx->px_ctr.p, 0, 4 * sizeof(u32), ctx->stream));
+  PoaExp const dev{x.dev, ctx->px_ctr.as<u32>()};
+  ctx->px = &dev;
+  int const rc = launch_msa(ctx, d, a.dev, v.dev);
+  ctx->px = nullptr;
+  MA_TRY(rc);
+  u32 hc[4] = {0, 0, 0, 0};
+  MA_HIP(ctx, hipMemcpyAsync(hc, ctx->px_ctr.p, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
+  MA_TRY(v.download(ctx));
+  MA_TRY(x.download(ctx));
+  if (ctx->memspace == MA_MEM_HOST)  // win_status may gain MA_W_VAR_OVERFLOW
+    MA_HIP(ctx, hipMemcpyAsync(asmb->win_status, a.dev.win_status, 4ull * d.n_windows, hipMemcpyDeviceToHost, ctx->stream));
+  MA_HIP(ctx, ma_stream_sync(ctx));
+  for (int k = 0; k < 4; ++k) ctx->poa_export_counts[k] = hc[k];
+  return MA_OK;
+}
+
+int ma_last_poa_export(ma_ctx_t* ctx, unsigned long long* out, int cap) {
+  if (!ctx || !out) return MA_ERR_ARG;
+  int n = 0;
+  for (; n < cap && n < 4; ++n) out[n] = ctx->poa_export_counts[n];
+  return n;
 }
 
 // the read metadata a call needs: none without the statistics over it (meta is then not read); all four arrays with them

@@ -63,6 +63,12 @@ struct KernelTimer {
 };
 
 struct GxDev;  // graph_ws.h: where a call that exports the graphs (ma_assemble_graph_batch) writes
+// where a call that exports the POA graphs (ma_msa_graph_batch) writes: the caller's arrays (device pointers), addressed by
+// GLOBAL window id, and the four pass counters of ma_last_poa_export
+struct PoaExp {
+  ma_poa_out_t o;
+  uint32_t* ctr;
+};
 
 }  // namespace ma
 
@@ -130,6 +136,11 @@ struct ma_ctx {
   // counters of ma_last_graph_export (device, read when asked for)
   const ma::GxDev* gx = nullptr;
   ma::DevBuf gx_mark, gx_routes;
+  // ma_msa_graph_batch: non-null while its POA stage runs (poa.hip: launch_msa takes the exporting kernels, host-counted
+  // rounds); the device counters of that call and the counts ma_last_poa_export reports
+  const ma::PoaExp* px = nullptr;
+  ma::DevBuf px_ctr;
+  unsigned long long poa_export_counts[4] = {0, 0, 0, 0};
   hipEvent_t sync_ev = nullptr;  // blocking-sync event: host threads sleep instead of spinning while the stream drains
   // host route (MA_MEM_HOST) of ma_process_batch, per lane: packed result records (pack.hip) and their pinned landing area
   ma::DevBuf pack_aux;

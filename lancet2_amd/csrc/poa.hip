@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "ma_internal.h"
@@ -2246,12 +2247,128 @@ __device__ __forceinline__ bool poa_window_skipped(MsaArgs const& A, int w) {
   return wide != (A.ws.pass == 2);
 }
 
+// ---- POA export (ma_msa_graph_batch): one component's finished graph and its MSA rows into the caller's arrays ----
+// Runs at the end of a component, after the bubble walk: the graph is still in LDS and the alignment scratch behind g.rowinfo
+// is free -- a membership mask per node (4 B), an MSA column per node (2 B) and one MSA row (1 B per column) go there.
+//  * letters and ranks come from nchar / node2rank; the out-edges are compacted by a block scan of nout, in id order, a node's
+//    edges in list order (pg_add_edge appends as spoa::Graph::AddEdge does);
+//  * a node belongs to the paths on its out-edges and on its in-edges (every edge ORs its labels onto its head), and to the
+//    path that starts at it (seq_first: the only source of a one-node path);
+//  * spoa's GenerateMultipleSequenceAlignment walks rank_to_node and gives a node and its aligned ring one column; the ring
+//    members follow their first member in rank (pg_toposort), so a column opens at every rank whose node is not in the ring
+//    of the rank before -- a prefix sum over rank;
+//  * a row is built in LDS ('-', then the letters of the member nodes at their columns) and copied out: no byte of the
+//    caller's array is written twice.
+// The running offsets of the component are the window's counts so far (thread 0 wrote them, thread 0 reads them back).
+template <class G>
+__device__ __forceinline__ void poa_export_component(G const& g, PoaExp const& X, int const w, size_t const ci, u32 const hap0, u32 const MH,
+                                                     int const tid) {
+  ma_poa_out_t const& o = X.o;
+  u32 const nn = ST.nn, ns = ST.nseq, PN = g.pn;
+  u32 const MN = static_cast<u32>(o.max_pnodes), ME = static_cast<u32>(o.max_pedges), MX = static_cast<u32>(o.max_cols);
+  LdsArr<u32> const mask{g.rowinfo.off};
+  LdsArr<u16> const colv{g.rowinfo.off + 4u * PN};
+  LdsArr<u8> const rowb{g.rowinfo.off + 6u * PN};
+  if (tid == 0) {
+    ST.red_r[0] = o.win_npnodes[w];
+    ST.red_r[1] = o.win_npedges[w];
+  }
+  for (u32 v = tid; v < nn; v += kT) mask[v] = 0;
+  __syncthreads();
+  u32 const pn0 = ST.red_r[0], pe0 = ST.red_r[1];
+  u32 const per = (nn + kT - 1) / kT;
+  u32 const lo = min(static_cast<u32>(tid) * per, nn), hi = min(lo + per, nn);
+  u32 cnt = 0;
+  for (u32 v = lo; v < hi; ++v) {
+    u32 const no = g.nout[v];
+    u32 m = 0;
+    for (u32 x = 0; x < no; ++x) {
+      u32 const l = g.lab(v * G::pe + x);
+      m |= l;
+      atomicOr(&mask[g.out_head[v * G::pe + x]], l);
+    }
+    if (m) atomicOr(&mask[v], m);
+    cnt += no;
+  }
+  if (static_cast<u32>(tid) < ns && ST.seq_first[tid] >= 0) atomicOr(&mask[static_cast<u32>(ST.seq_first[tid])], 1u << tid);
+  u32 ne = 0;
+  u32 at = block_excl_scan(cnt, tid, ne);
+  // MSA columns, over rank (nrank == nn: every node is ranked)
+  auto const opens = [&](u32 r) {
+    if (r == 0) return true;
+    u32 const node = g.rank2node[r], prev = g.rank2node[r - 1];
+    u32 const na = g.nal[prev];
+    bool op = true;
+    for (u32 y = 0; y < na; ++y) op = op && g.al[prev * G::pe + y] != node;
+    return op;
+  };
+  u32 nopen = 0;
+  for (u32 r = lo; r < hi; ++r) nopen += opens(r) ? 1u : 0u;
+  u32 ncols = 0;
+  u32 col = block_excl_scan(nopen, tid, ncols);
+  for (u32 r = lo; r < hi; ++r) {
+    col += opens(r) ? 1u : 0u;
+    colv[g.rank2node[r]] = static_cast<u16>(col - 1u);
+  }
+  __syncthreads();
+  bool const nfit = pn0 + nn <= MN, efit = pe0 + ne <= ME, cfit = ncols <= MX;
+  if (nfit) {
+    size_t const nb = static_cast<size_t>(w) * MN + pn0;
+    for (u32 v = tid; v < nn; v += kT) {
+      o.pnode_base[nb + v] = g.nchar[v];
+      o.pnode_rank[nb + v] = g.node2rank[v];
+      o.pnode_col[nb + v] = colv[v];
+      o.pnode_haps[nb + v] = mask[v];
+    }
+  }
+  if (efit) {
+    size_t const eb = static_cast<size_t>(w) * ME + pe0;
+    for (u32 v = lo; v < hi; ++v) {
+      u32 const no = g.nout[v];
+      for (u32 x = 0; x < no; ++x) {
+        o.pedge_tail[eb + at] = v;
+        o.pedge_head[eb + at] = g.out_head[v * G::pe + x];
+        o.pedge_haps[eb + at] = g.lab(v * G::pe + x);
+        ++at;
+      }
+    }
+  }
+  if (static_cast<u32>(tid) < ns) o.hap_first[static_cast<size_t>(w) * MH + hap0 + tid] = static_cast<u32>(ST.seq_first[tid]);
+  if (cfit) {
+    for (u32 h = 0; h < ns; ++h) {
+      for (u32 k = tid; k < ncols; k += kT) rowb[k] = '-';
+      __syncthreads();
+      for (u32 v = tid; v < nn; v += kT)
+        if ((mask[v] >> h) & 1u) rowb[colv[v]] = g.nchar[v];
+      __syncthreads();
+      u8* const dst = o.msa + (static_cast<size_t>(w) * MH + hap0 + h) * MX;
+      for (u32 k = tid; k < ncols; k += kT) dst[k] = rowb[k];
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {
+    o.comp_pnode0[ci] = pn0;
+    o.comp_npnodes[ci] = nn;
+    o.comp_pedge0[ci] = pe0;
+    o.comp_npedges[ci] = ne;
+    o.comp_ncols[ci] = ncols;
+    o.win_npnodes[w] = pn0 + nn;
+    o.win_npedges[w] = pe0 + ne;
+    o.win_ncols[w] = max(o.win_ncols[w], ncols);
+    u32 const st = (nfit ? 0u : static_cast<u32>(MA_P_NODE_OVERFLOW)) | (efit ? 0u : static_cast<u32>(MA_P_EDGE_OVERFLOW)) |
+                   (cfit ? 0u : static_cast<u32>(MA_P_COL_OVERFLOW));
+    if (st) o.win_pstatus[w] |= st;
+  }
+  __syncthreads();
+}
+
 // One window's POA up to its next banded fill (returns kMsaYield: the LDS block is saved, the pending alignment's descriptors
 // are in the image) or to its end (kMsaDone).  `resume`: continue from the image after a fill.  Runs as the body of k_msa
 // (host-counted rounds, MA_POA_SCHED=0) and as the G job of the persistent kernel k_poa.
 constexpr u32 kMsaDone = 0, kMsaYield = 1;
-template <int CWMAX, bool LAB32, int PE>
-__device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool const resume_in) {
+// EXPORT (ma_msa_graph_batch: k_msa<.., true>, X = where to): every component's graph is written out behind its bubble walk.
+template <int CWMAX, bool LAB32, int PE, bool EXPORT = false>
+__device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool const resume_in, PoaExp const* const X = nullptr) {
   int const tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int const w = A.win0 + lw;
   ma_params_t const& P = A.prm;
@@ -2325,6 +2442,16 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
     ST.filled = 0;
     ST.pending = 0;
     ST.c_cur = ST.h_cur = 0;
+  }
+  if constexpr (EXPORT) {
+    // a window that starts (again: a retry pass) has nothing exported
+    if (!resume && tid == 0) {
+      for (int c = 0; c < MC; ++c) {
+        size_t const ci = static_cast<size_t>(w) * MC + c;
+        X->o.comp_pnode0[ci] = X->o.comp_npnodes[ci] = X->o.comp_pedge0[ci] = X->o.comp_npedges[ci] = X->o.comp_ncols[ci] = 0;
+      }
+      X->o.win_pstatus[w] = X->o.win_npnodes[w] = X->o.win_npedges[w] = X->o.win_ncols[w] = 0;
+    }
   }
   __syncthreads();
   PROF_T0();
@@ -3088,6 +3215,10 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
       }
       __syncthreads();
     }
+    if constexpr (EXPORT) {
+      __syncthreads();
+      if (!ST.overflow && ST.nn > 0) poa_export_component(g, *X, w, ci, hap0, static_cast<u32>(MH), tid);
+    }
     // (bits 1 and up: what the GRAPH overflowed for, if it did -- a caller's cap leaves them 0; for PoaWs::cause below)
     if (tid == 0 && overflow) ST.win_overflow = 1u | (ST.overflow << 1);
     PROF_ACC(5);
@@ -3117,6 +3248,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
       ST.done = 1;
       ST.pending = 0;
     }
+    if constexpr (EXPORT) atomicAdd(&X->ctr[ws.pass >= 5 ? 3u : (ws.pass >= 3 ? 2u : ((ws.pass == 2 || (ws.pass == 0 && LAB32)) ? 1u : 0u))], 1u);
   }
   if (ws.split) {
     __syncthreads();
@@ -3125,9 +3257,13 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
   return kMsaDone;
 }
 
-template <int CWMAX, bool LAB32, int PE>
-__global__ __launch_bounds__(kT, LAB32 ? 1 : 2) void k_msa(MsaArgs A) {
-  (void)msa_window<CWMAX, LAB32, PE>(A, static_cast<int>(blockIdx.x), A.round > 0);
+struct MsaArgsX : MsaArgs {
+  PoaExp x;
+};
+template <int CWMAX, bool LAB32, int PE, bool EXPORT = false>
+__global__ __launch_bounds__(kT, LAB32 ? 1 : 2) void k_msa(std::conditional_t<EXPORT, MsaArgsX, MsaArgs> A) {
+  if constexpr (EXPORT) (void)msa_window<CWMAX, LAB32, PE, true>(A, static_cast<int>(blockIdx.x), A.round > 0, &A.x);
+  else (void)msa_window<CWMAX, LAB32, PE>(A, static_cast<int>(blockIdx.x), A.round > 0);
 }
 
 // The row descriptors of a pending alignment, read straight from the window's LDS image in HBM: every access is
@@ -3732,7 +3868,9 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   // MA_POA_SCHED: 1 (default) = the persistent kernel k_poa schedules the windows on the device; 0 = rounds 3-5's host-counted
   // rounds of k_msa / k_msa_band (same device code: msa_window, band_job; same results, tested)
   // (a retry pass takes the host-counted rounds: a handful of windows, and the persistent kernel is not built for eight slots)
-  bool const sched = !retry && ws.split && ws.lean && !(getenv("MA_POA_SCHED") && atoi(getenv("MA_POA_SCHED")) == 0);
+  // (an exporting call -- ma_msa_graph_batch -- likewise: the exporting kernels are k_msa's)
+  bool const exporting = ctx->px != nullptr;
+  bool const sched = !retry && !exporting && ws.split && ws.lean && !(getenv("MA_POA_SCHED") && atoi(getenv("MA_POA_SCHED")) == 0);
   ws.full_by_worker = sched ? 1u : 0u;
   // workgroups of the persistent kernel: what the chip holds at once (two per CU while the graph fits 80 KB of LDS; a lane
   // that runs beside others may be told to take one -- MA_POA_WGS_PER_CU -- and leave the other half of every CU's LDS to them)
@@ -3768,8 +3906,13 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
                     : (max_len <= 1024 ? k_msa<4, false, 4> : (max_len <= 2048 ? k_msa<8, false, 4> : k_msa<16, false, 4>));
   if (pe == 8)  // (poa_retry_max_hap_len(*, 8) < 2048: the widest column tier is never needed)
     kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 8> : k_msa<8, true, 8>) : (max_len <= 1024 ? k_msa<4, false, 8> : k_msa<8, false, 8>);
-  MA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(lds)));
+  auto kernx = lab32 ? (max_len <= 1024 ? k_msa<4, true, 4, true> : (max_len <= 2048 ? k_msa<8, true, 4, true> : k_msa<16, true, 4, true>))
+                     : (max_len <= 1024 ? k_msa<4, false, 4, true> : (max_len <= 2048 ? k_msa<8, false, 4, true> : k_msa<16, false, 4, true>));
+  if (pe == 8)
+    kernx = lab32 ? (max_len <= 1024 ? k_msa<4, true, 8, true> : k_msa<8, true, 8, true>)
+                  : (max_len <= 1024 ? k_msa<4, false, 8, true> : k_msa<8, false, 8, true>);
+  MA_HIP(ctx, hipFuncSetAttribute(exporting ? reinterpret_cast<const void*>(kernx) : reinterpret_cast<const void*>(kern),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
   auto pkern = lab32 ? (max_len <= 1024 ? k_poa<4, true> : (max_len <= 2048 ? k_poa<8, true> : k_poa<16, true>))
                      : (max_len <= 1024 ? k_poa<4, false> : (max_len <= 2048 ? k_poa<8, false> : k_poa<16, false>));
   if (sched)
@@ -3801,6 +3944,14 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
       if (!sched) MA_HIP(ctx, hipMemsetAsync(ctr, 0, 64, ctx->stream));
     }
     MsaArgs args{b, a, o, ws, P, win0, 0u, 0u};
+    auto const run_k_msa = [&]() {
+      if (exporting) {
+        MsaArgsX ax{args, *ctx->px};
+        hipLaunchKernelGGL(kernx, dim3(nwin), dim3(kT), lds, ctx->stream, ax);
+      } else {
+        hipLaunchKernelGGL(kern, dim3(nwin), dim3(kT), lds, ctx->stream, args);
+      }
+    };
     if (sched) {
       char* qb = reinterpret_cast<char*>(ws.pending_ctr) + 256;
       PoaSched* const S = reinterpret_cast<PoaSched*>(qb);
@@ -3831,7 +3982,7 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
     } else if (!ws.split) {
       args.finish = 1;
       ctx->tic("k_msa");
-      hipLaunchKernelGGL(kern, dim3(nwin), dim3(kT), lds, ctx->stream, args);
+      run_k_msa();
       ctx->toc();
     } else {
       // Per-window progress: k_msa runs every window up to its next banded fill (or to its end); while many windows wait
@@ -3844,7 +3995,7 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
         args.round = r;
         args.finish = 0;
         ctx->tic("k_msa");
-        hipLaunchKernelGGL(kern, dim3(nwin), dim3(kT), lds, ctx->stream, args);
+        run_k_msa();
         ctx->toc();
         u32 pend2[2] = {0, 0};
         MA_HIP(ctx, hipMemcpyAsync(pend2, ws.pending_ctr, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3860,7 +4011,7 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
           args.round = r + 1;
           args.finish = 1;
           ctx->tic("k_msa");
-          hipLaunchKernelGGL(kern, dim3(nwin), dim3(kT), lds, ctx->stream, args);
+          run_k_msa();
           ctx->toc();
           break;
         }

@@ -55,6 +55,9 @@ def load_library(path=None):
     if hasattr(lib, "ma_assemble_graph_batch"):  # (likewise: a build of before the graph export)
         lib.ma_assemble_graph_batch.argtypes = [C.c_void_p] * 4
         lib.ma_last_graph_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+    if hasattr(lib, "ma_msa_graph_batch"):  # (likewise: a build of before the POA export)
+        lib.ma_msa_graph_batch.argtypes = [C.c_void_p] * 5
+        lib.ma_last_poa_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     return lib
 
 
@@ -177,6 +180,31 @@ class Engine:
         o = capi.fill_struct(capi.VarOut, out)
         self._check(self.lib.ma_msa_batch(self.h, C.byref(b), C.byref(a), C.byref(o)), "ma_msa_batch")
         return out
+
+    def msa_graph(self, arrs, n, nr, asm, max_pnodes=4096, max_pedges=8192, max_cols=4096):
+        """ma_msa_graph_batch: msa() + the SPOA graph and the MSA rows of every component (capi.poa_out_spec; max_pnodes and
+        max_pedges are per window, max_cols per component).  Returns (var, poa); poa also carries the three caps under their
+        names.  `asm`'s win_status may gain MA_W_VAR_OVERFLOW, as in msa()."""
+        out = self._alloc(capi.var_out_spec(self.p, n))
+        px = self._alloc(capi.poa_out_spec(self.p, n, max_pnodes, max_pedges, max_cols))
+        b = capi.make_batch_struct(arrs, n, nr)
+        self.msa_graph_device(b, capi.fill_struct(capi.AsmOut, asm), capi.fill_struct(capi.VarOut, out),
+                              capi.make_poa_struct(px, max_pnodes, max_pedges, max_cols))
+        px.update(max_pnodes=int(max_pnodes), max_pedges=int(max_pedges), max_cols=int(max_cols))
+        return out, px
+
+    def msa_graph_device(self, batch_struct, asm, var, poa):
+        """ma_msa_graph_batch on caller-made structs (either memory space); poa=None: a null pointer, the plain call"""
+        self._check(self.lib.ma_msa_graph_batch(self.h, C.byref(batch_struct), C.byref(asm), C.byref(var),
+                                                C.byref(poa) if poa is not None else None), "ma_msa_graph_batch")
+
+    def last_poa_export(self):
+        """Windows the last msa_graph() ran with the export, per kind of pass (include/microasm.h: ma_last_poa_export)"""
+        buf = (C.c_ulonglong * 4)()
+        n = self.lib.ma_last_poa_export(self.h, buf, 4)
+        if n < 0:
+            raise EngineError(f"ma_last_poa_export failed ({n})")
+        return {k: int(buf[i]) for i, k in enumerate(capi.POA_EXPORT_KEYS) if i < n}
 
     def genotype(self, arrs, n, nr, asm, var, debug=True):
         out = self._alloc(capi.geno_out_spec(self.p, n, nr, debug))

@@ -1839,4 +1839,53 @@ inline std::string RenderComponentDot(const ma_params_t& p, const ma_asm_out_t& 
   return os.str();
 }
 
+// ---- MSA snapshots: the GFA and the FASTA of one exported component (ma_msa_graph_batch) ------------------------------------
+// Character for character what MsaBuilder::BuildGfaString / BuildFastaString print (caller/msa_builder.cpp:44-102): a segment
+// per POA node (its id + 1) followed by the links of its out-edges, a path per haplotype (ref0, hap1, ...) walked from
+// hap_first along the edges that carry the haplotype's label; the gapped rows.  Both return the empty string when the
+// window's export is flagged (ma_pstatus) or the component has no node.
+inline std::string RenderComponentGfa(const ma_params_t& p, const ma_asm_out_t& a, const ma_poa_out_t& x, int w, uint32_t comp) {
+  size_t const W = static_cast<size_t>(w), MN = static_cast<size_t>(x.max_pnodes), ME = static_cast<size_t>(x.max_pedges);
+  size_t const ci = W * static_cast<size_t>(p.max_comps) + comp;
+  uint32_t const nn = x.comp_npnodes[ci], ne = x.comp_npedges[ci];
+  if (x.win_pstatus[W] != 0 || nn == 0) return {};
+  size_t const nb = W * MN + x.comp_pnode0[ci], eb = W * ME + x.comp_pedge0[ci];
+  std::vector<uint32_t> first_edge(nn + 1, ne);  // a node's edges are contiguous, nodes in id order
+  for (uint32_t e = ne; e-- > 0;) first_edge[x.pedge_tail[eb + e]] = e;
+  for (uint32_t v = nn; v-- > 0;) first_edge[v] = std::min(first_edge[v], first_edge[v + 1]);
+  std::string out = "H\tVN:Z:1.0\n";
+  for (uint32_t v = 0; v < nn; ++v) {
+    out += "S\t" + std::to_string(v + 1) + "\t" + static_cast<char>(x.pnode_base[nb + v]) + "\n";
+    for (uint32_t e = first_edge[v]; e < first_edge[v + 1]; ++e)
+      out += "L\t" + std::to_string(v + 1) + "\t+\t" + std::to_string(x.pedge_head[eb + e] + 1) + "\t+\t0M\n";
+  }
+  uint32_t const hap0 = a.comp_hap0[ci], nh = a.comp_nhaps[ci];
+  for (uint32_t h = 0; h < nh; ++h) {
+    out += std::string("P\t") + (h == 0 ? "ref" : "hap") + std::to_string(h) + "\t";
+    uint32_t cur = x.hap_first[W * static_cast<size_t>(p.max_haps) + hap0 + h];
+    for (uint32_t steps = 0; cur < nn && steps < nn; ++steps) {
+      out += (steps ? "," : "") + std::to_string(cur + 1) + "+";
+      uint32_t next = UINT32_MAX;
+      for (uint32_t e = first_edge[cur]; e < first_edge[cur + 1] && next == UINT32_MAX; ++e)
+        if ((x.pedge_haps[eb + e] >> h) & 1u) next = x.pedge_head[eb + e];
+      cur = next;
+    }
+    out += "\t*\n";
+  }
+  return out;
+}
+
+inline std::string RenderComponentFasta(const ma_params_t& p, const ma_asm_out_t& a, const ma_poa_out_t& x, int w, uint32_t comp) {
+  size_t const W = static_cast<size_t>(w), MX = static_cast<size_t>(x.max_cols);
+  size_t const ci = W * static_cast<size_t>(p.max_comps) + comp;
+  if (x.win_pstatus[W] != 0 || x.comp_npnodes[ci] == 0) return {};
+  uint32_t const hap0 = a.comp_hap0[ci], nh = a.comp_nhaps[ci], ncols = x.comp_ncols[ci];
+  std::string out;
+  for (uint32_t h = 0; h < nh; ++h) {
+    const char* row = reinterpret_cast<const char*>(x.msa) + (W * static_cast<size_t>(p.max_haps) + hap0 + h) * MX;
+    out += std::string(">") + (h == 0 ? "ref" : "hap") + std::to_string(h) + "\n" + std::string(row, ncols) + "\n";
+  }
+  return out;
+}
+
 }  // namespace lancet2_amd::host

@@ -22,6 +22,7 @@ for src in sorted(glob.glob(os.path.join(R, "lancet2_amd", "csrc", "*.hip"))):
             name = re.sub(r"\(anonymous namespace\)::", "", name)
             name = re.sub(r"^void ", "", name).replace("ma::", "")
             name = re.sub(r"\((GArgs|EvStatArgs|MsaArgs|CleanArgs|ChainArgs|CxArgs|DBatch|GraphWs|ma_asm_out|unsigned|RegClass2|KeyBase)[^)]*\)$", "", name)
+            name = re.sub(r"\(std::conditional<(true|false), MsaArgsX, MsaArgs>::type\)$", "", name)  # k_msa<.., EXPORT>
             cur = {"file": os.path.basename(src), "kernel": name[:72]}
             rows.append(cur)
             continue
