@@ -12,8 +12,8 @@
 //    returns; the workgroup that takes the window after its fill restores the block and continues (best end cell,
 //    certificate, traceback, graph update, toposort, variants).
 //  * F jobs (band_job) -- ONE wavefront fills a band of 64 / 128 / 256 columns around every row's backbone coordinate
-//    (poa_fill_lean / poa_fill_band), reading the descriptors straight from the saved block.  The band is exact by
-//    certificate (see poa_fill_band) or the alignment is redone with the next tier, at last with the full fill.
+//    (poa_fill_lean), reading the descriptors straight from the saved block.  The band is exact by
+//    certificate (see poa_fill_lean) or the alignment is redone with the next tier, at last with the full fill.
 //  (k_msa / k_msa_band run the same two bodies as rounds the host counts: MA_POA_SCHED=0, the scheduling of rounds 3-5.)
 //  * Full fill (poa_fill<CW>, fallback and MA_POA_BAND=0): row-synchronous, all 256 lanes work on ONE DP row, lane l
 //    owns CW consecutive columns; the horizontal gap chains (E, Q) are closed with two prefix maxima over the row
@@ -97,7 +97,6 @@ struct PoaWs {
   u32* pending_ctr;  // split mode: windows that yielded in the current k_msa launch
   u32 no_direct;     // MA_POA_NO_DIRECT: every alignment goes through a fill (tests: the shortcut changes nothing)
   u32 raw_cap;       // MA_POA_RAW_CAP: bytes per haplotype of the bubble walk's LDS scratch (tests: forces the HBM route)
-  u32 lean;          // band tiers run poa_fill_lean (default) / poa_fill_band (MA_POA_LEAN=0; same codes, tested)
   u32 lab32;         // this pass runs the kernels with 32-bit label masks (components of 17 .. 32 haplotypes)
   u32 pass;          // 0: every window; 1: only windows whose components all hold <= 16 haplotypes; 2: only the others
                      // retry passes (ma_set_poa_retry), over the windows `cause` marks: 3 / 4: marked for the slot width,
@@ -945,11 +944,13 @@ __device__ __forceinline__ void poa_fill(G const& g, PoaWs const& ws, u16* codes
 #endif
 }
 
-// ---- banded fill (wave 0 only): 256 columns around the expected diagonal, exact by certificate ----
+__device__ __forceinline__ i32 wave_shl1(i32 x, i32 fill) { return dpp_mov<0x130, 0xF>(x, fill); }  // lane l <- lane l + 1
+
+// ---- banded fill (one wavefront): 64 / 128 / 256 columns around the expected diagonal, exact by certificate ----
 // Haplotypes differ from the graph's backbone by a few variants, so the optimal path stays close to the
-// diagonal "column = backbone coordinate of the row's node".  Row i gets the 256-column window
-// [j0(i), j0(i) + 255] (j0 = 1 mod 4) centred on that coordinate and ONE wavefront fills it: no barriers, no
-// LDS exchange, a quarter of the cells.
+// diagonal "column = backbone coordinate of the row's node".  Row i gets the window of BW = 64 CW columns
+// [j0(i), j0(i) + BW - 1] (j0 = 1 mod CW) centred on that coordinate and ONE wavefront fills it: no barriers, no
+// LDS exchange, a quarter of the cells at the widest tier.
 // Everything outside the window counts as minus infinity.  Exactness is certified afterwards:
 //   every way a path can leave the band passes through an "exit" cell (a window cell whose up / diagonal /
 //   right successor lies outside the successor row's window; row 0 / column 0 cells next to uncovered
@@ -958,462 +959,30 @@ __device__ __forceinline__ void poa_fill(G const& g, PoaWs const& ws, u16* codes
 //   (a) S is the true optimum, (b) every DP value the backtrack can test at a path cell is either one it
 //   compares against a value >= S (then equality forces exactness on both sides) or a gap-state value that
 //   is >= its path neighbour's H - 26 >= S - 26 > E, hence also attained inside the band: the banded
-//   decision codes along the path equal the full DP's.  Otherwise the caller repeats the row-synchronous
-//   full fill.
-// Lane l owns the four window columns j0 + 4 l .. j0 + 4 l + 3.  When the window slides (always by a multiple
-// of four columns, usually one lane every four rows) the register rows slide with it: a whole-wave DPP shift;
+//   decision codes along the path equal the full DP's.  Otherwise the caller repeats the alignment with the
+//   next tier, at last with the row-synchronous full fill.
+// Lane l owns the CW window columns j0 + CW l .. j0 + CW l + CW - 1.  When the window slides (always by a multiple
+// of CW columns, usually one lane every few rows) the register row slides with it: a whole-wave DPP shift;
 // the columns that fall off the left edge are exits, the ones that enter start at minus infinity.
-__device__ __forceinline__ i32 wave_shl1(i32 x, i32 fill) { return dpp_mov<0x130, 0xF>(x, fill); }  // lane l <- lane l + 1
-// the same, IN PLACE (the result is tied to x's own register, lane 63 is patched afterwards): written the other way the
-// compiler gives the shifted rows new registers and pays 28 copies on every row that does NOT slide
-__device__ __forceinline__ void wave_shl1_inplace(i32& x, i32 fill, bool last_lane) {
-  x = __builtin_amdgcn_update_dpp(x, x, 0x130, 0xF, 0xF, false);
-  x = last_lane ? fill : x;
-}
-__device__ __forceinline__ void wave_shr1_inplace(i32& x, i32 fill, bool first_lane) {  // lane l <- lane l - 1
-  x = __builtin_amdgcn_update_dpp(x, x, 0x138, 0xF, 0xF, false);
-  x = first_lane ? fill : x;
-}
-
-template <int CW, class G>
-__device__ void poa_fill_band(G const& g, u32 const w_stride, size_t const plane, u16* codes, i32* rows, i32* hlast, u32 V,
-                              u32 L, int lane, const u8* seq, i32* edge_out) {
-  static_assert(CW == 1 || CW == 2 || CW == 4, "band tiers: 64, 128 or 256 columns");
-  constexpr u32 BW = 64u * CW;  // columns of the band
-  constexpr i32 NEG = kScanIdent;
-  i32 jr[CW];  // this lane's columns relative to the window
-#pragma unroll
-  for (int c = 0; c < CW; ++c) jr[c] = CW * lane + c;
-  i32 HA[CW], FA[CW], OA[CW], HB[CW], FB[CW], OB[CW];  // the two previous rows, roles alternating (see `row`)
-#pragma unroll
-  for (int c = 0; c < CW; ++c) HA[c] = FA[c] = OA[c] = HB[c] = FB[c] = OB[c] = kNegInf;
-  u32 sc[CW];
-  i32 edge = kNegInf;
-  u32 info = g.rowinfo[1];
-  u32 depth = g.rowdepth[1];
-  u32 j0n = g.rowj0[1];
-  u32 j0 = j0n;  // window the register rows are aligned to
-  auto load_sc = [&]() {
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      u32 const j = j0 + static_cast<u32>(CW) * lane + c;
-      sc[c] = (j >= 1 && j <= L) ? seq[j - 1] : 0u;
-    }
-  };
-  load_sc();
-  // the four characters that enter at lane 63 on the next one-lane slide (uniform; fetched one slide ahead)
-  u32 sc_in[CW];
-  auto load_sc_in = [&]() {
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      u32 const j = j0 + BW + c;
-      sc_in[c] = j <= L ? g.ubyte(seq + (j - 1)) : 0u;
-    }
-  };
-  load_sc_in();
-  // one row: (H1, F1, O1) is row i - 1, (H2, F2, O2) row i - 2 -- which row i then OVERWRITES: the caller swaps the two
-  // register sets from row to row instead of rotating them (24 copies a row, and as many again where the compiler
-  // split the rotation across the loop edge)
-  auto row = [&](u32 const i, i32(&H1)[CW], i32(&F1)[CW], i32(&O1)[CW], i32(&H2)[CW], i32(&F2)[CW], i32(&O2)[CW])
-                 __attribute__((always_inline)) {
-    u32 const nch = info & 0xFFu, np = ri_np<G::pe>(info);
-    bool const fast = info & RI_FAST, store = info & RI_STORE;
-    u32 const info_cur = info;
-    i32 const h0 = col0_h(depth);
-    u32 const j0_new = j0n;
-    if (i < V) {
-      info = g.rowinfo[i + 1];
-      depth = g.rowdepth[i + 1];
-      j0n = g.rowj0[i + 1];
-    }
-    // ---- slide the register rows to this row's window ----
-    if (__builtin_expect(j0_new != j0, 0)) {  // (one row in four: the register copies belong on this side)
-      i32 const sh = (static_cast<i32>(j0_new) - static_cast<i32>(j0)) / CW;  // lanes; > 0: window moves right
-      // columns that fall off: they had no successor inside the band
-      {
-        bool const dropped = sh > 0 ? lane < sh : lane >= 64 + sh;
-        u32 const jbo = j0 + static_cast<u32>(CW) * lane;
-        if (dropped) {
-#pragma unroll
-          for (int c = 0; c < CW; ++c)
-            if (jbo + c >= 1 && jbo + c <= L) edge = max(edge, max(H1[c], H2[c]));
-        }
-      }
-      // one lane at a time, every register IN PLACE (almost always a single step to the right); a second code path
-      // that builds the shifted rows in new registers costs two dozen copies on every row that does not slide
-      while (j0 < j0_new) {
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          wave_shl1_inplace(H1[c], kNegInf, lane == 63);
-          wave_shl1_inplace(F1[c], kNegInf, lane == 63);
-          wave_shl1_inplace(O1[c], kNegInf, lane == 63);
-          wave_shl1_inplace(H2[c], kNegInf, lane == 63);
-          wave_shl1_inplace(F2[c], kNegInf, lane == 63);
-          wave_shl1_inplace(O2[c], kNegInf, lane == 63);
-          i32 t = static_cast<i32>(sc[c]);
-          wave_shl1_inplace(t, static_cast<i32>(sc_in[c]), lane == 63);
-          sc[c] = static_cast<u32>(t);
-        }
-        j0 += CW;
-        load_sc_in();
-      }
-      if (j0 > j0_new) {  // rare: the backbone coordinate steps back
-        do {
-          j0 -= CW;
-#pragma unroll
-          for (int c = 0; c < CW; ++c) {
-            wave_shr1_inplace(H1[c], kNegInf, lane == 0);
-            wave_shr1_inplace(F1[c], kNegInf, lane == 0);
-            wave_shr1_inplace(O1[c], kNegInf, lane == 0);
-            wave_shr1_inplace(H2[c], kNegInf, lane == 0);
-            wave_shr1_inplace(F2[c], kNegInf, lane == 0);
-            wave_shr1_inplace(O2[c], kNegInf, lane == 0);
-            u32 const j = j0 + c;
-            i32 t = static_cast<i32>(sc[c]);
-            wave_shr1_inplace(t, (j >= 1 && j <= L) ? static_cast<i32>(seq[j - 1]) : 0, lane == 0);
-            sc[c] = static_cast<u32>(t);
-          }
-        } while (j0 > j0_new);
-        load_sc_in();
-      }
-    }
-    u32 const jb = j0 + static_cast<u32>(CW) * lane;
-    // ---- vertical + diagonal part ----
-    i32 hh[CW], ff[CW], oo[CW], hmv[CW];
-    // H(pr, jb - 1) from the left neighbour lane's last column, column 0 at the matrix edge, -inf at the band edge
-    auto left_of = [&](i32 last_col_value, u32 pr) -> i32 {
-      i32 const v = wave_shr1(last_col_value, kNegInf);
-      if (lane != 0) return v;
-      return jb == 1 ? (pr == 0 ? 0 : col0_h(g.rowdepth[pr])) : kNegInf;
-    };
-    // a stored row restricted to this window (its own window may sit elsewhere)
-    auto fetch_store = [&](u32 pr, i32(&th)[CW], i32(&tf)[CW], i32(&to)[CW], i32& thd) {
-      u32 const pj0 = g.rowj0[pr];
-      int const d = (static_cast<i32>(j0) - static_cast<i32>(pj0)) / CW;  // this lane reads the stored lane l + d
-      int const sl = lane + d;
-      bool const in = sl >= 0 && sl < 64;
-      u32 const slot = g.rowslot[pr];
-      const i32* base = rows + static_cast<size_t>(slot) * 3 * w_stride;
-#pragma unroll
-      for (int c = 0; c < CW; ++c) th[c] = tf[c] = to[c] = kNegInf;
-      if (in) {
-        if constexpr (CW == 4) {
-          int4 const vh = *reinterpret_cast<const int4*>(base + 4 * sl);
-          int4 const vf = *reinterpret_cast<const int4*>(base + w_stride + 4 * sl);
-          int4 const vo = *reinterpret_cast<const int4*>(base + 2 * static_cast<size_t>(w_stride) + 4 * sl);
-          th[0] = vh.x; th[1] = vh.y; th[2] = vh.z; th[3] = vh.w;
-          tf[0] = vf.x; tf[1] = vf.y; tf[2] = vf.z; tf[3] = vf.w;
-          to[0] = vo.x; to[1] = vo.y; to[2] = vo.z; to[3] = vo.w;
-        } else if constexpr (CW == 2) {
-          int2 const vh = *reinterpret_cast<const int2*>(base + 2 * sl);
-          int2 const vf = *reinterpret_cast<const int2*>(base + w_stride + 2 * sl);
-          int2 const vo = *reinterpret_cast<const int2*>(base + 2 * static_cast<size_t>(w_stride) + 2 * sl);
-          th[0] = vh.x; th[1] = vh.y;
-          tf[0] = vf.x; tf[1] = vf.y;
-          to[0] = vo.x; to[1] = vo.y;
-        } else {
-          th[0] = base[sl];
-          tf[0] = base[w_stride + sl];
-          to[0] = base[2 * static_cast<size_t>(w_stride) + sl];
-        }
-      }
-      // H(pr, jb - 1): the stored column just left of this lane's first one
-      i32 hd = kNegInf;
-      if (jb == 1) {
-        hd = col0_h(g.rowdepth[pr]);
-      } else if (sl >= 1 && sl <= 64) {
-        hd = base[CW * sl - 1];
-      }
-      thd = hd;
-      // stored columns this window does not cover are exits of row pr towards this row
-      if (d != 0) {
-        int const ml = lane;  // stored lane inspected by this lane
-        bool const dropped = d > 0 ? ml < d : ml >= 64 + d;
-        if (dropped) {
-          u32 const xj = pj0 + static_cast<u32>(CW) * ml;
-#pragma unroll
-          for (int c = 0; c < CW; ++c)
-            if (xj + c <= L) edge = max(edge, base[CW * ml + c]);
-        }
-      }
-    };
-    auto fetch = [&](u32 pr, i32(&th)[CW], i32(&tf)[CW], i32(&to)[CW], i32& thd) {
-      if (pr == 0) {
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          th[c] = row0_h(jb + c);
-          tf[c] = kNegInf;
-          to[c] = kNegInf;
-        }
-        thd = row0_h(jb - 1);
-      } else if (pr + 1 == i) {
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          th[c] = H1[c];
-          tf[c] = F1[c];
-          to[c] = O1[c];
-        }
-        thd = left_of(H1[CW - 1], pr);
-      } else if (pr + 2 == i) {
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          th[c] = H2[c];
-          tf[c] = F2[c];
-          to[c] = O2[c];
-        }
-        thd = left_of(H2[CW - 1], pr);
-      } else {
-        fetch_store(pr, th, tf, to, thd);
-      }
-    };
-    u32 const npe = np ? np : 1u;
-    if (fast) {
-      i32 hd = left_of(H1[CW - 1], i - 1);
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        i32 const ph = H1[c];
-        ff[c] = max(F1[c] + E_, ph + G_);
-        oo[c] = max(O1[c] + C_, ph + Q_);
-        hmv[c] = hd + ((nch == sc[c]) ? M_ : N_);
-        hd = ph;
-      }
-    } else {
-      for (u32 x = 0; x < npe; ++x) {
-        u32 const pr = np ? pred_row(g, i, info_cur, x) : 0u;
-        i32 th[CW], tf[CW], to[CW], hd;
-        fetch(pr, th, tf, to, hd);
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          i32 const fv = max(tf[c] + E_, th[c] + G_), ov = max(to[c] + C_, th[c] + Q_);
-          i32 const hv = hd + ((nch == sc[c]) ? M_ : N_);
-          hd = th[c];
-          if (x == 0) {
-            ff[c] = fv;
-            oo[c] = ov;
-            hmv[c] = hv;
-          } else {
-            ff[c] = max(ff[c], fv);
-            oo[c] = max(oo[c], ov);
-            hmv[c] = max(hmv[c], hv);
-          }
-        }
-      }
-      // row 0 ground that this window does not cover (a node without in-edges hangs off the virtual start row)
-      if (np == 0 && j0 + BW <= L) edge = max(edge, row0_h(j0 + BW));
-      if (np == 0 && j0 > 1) edge = max(edge, row0_h(1));
-    }
-    // the previous rows' cell whose diagonal successor would be the column right of this window
-    if (lane == 63 && jb + CW - 1 < L) edge = max(edge, max(H1[CW - 1], H2[CW - 1]));
-    // column 0 of this row is an exit when the window does not start at column 1
-    if (j0 > 1) edge = max(edge, h0);
-    // ---- prefix maxima over the window (column 0 enters through lane 0 when the window starts at column 1) ----
-    // (columns beyond L are filled like any other: a cell only feeds cells to its right and below, so what they hold
-    //  never reaches a column <= L; nothing reads them.  Column indices are taken RELATIVE to the window, jr = j - j0:
-    //  the same maxima up to a per-row constant that cancels below, and jr is a loop invariant of the lane)
-    bool const col0 = j0 == 1 && lane == 0;  // column 0 (jr = -1) enters through lane 0
-    i32 run1 = col0 ? h0 - 1 : NEG, run2 = col0 ? h0 - 2 : NEG;
-    i32 a1r[CW], a2r[CW];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      i32 const m = max(hmv[c], max(ff[c], oo[c]));
-      hh[c] = m;
-      a1r[c] = m + jr[c];
-      a2r[c] = a1r[c] + jr[c];
-      run1 = max(run1, a1r[c]);
-      run2 = max(run2, a2r[c]);
-    }
-    i32 const inc1 = wave_incl_max(run1, NEG), inc2 = wave_incl_max(run2, NEG);
-    i32 s1 = wave_shr1(inc1, NEG), s2 = wave_shr1(inc2, NEG);
-    if (col0) {
-      s1 = h0 - 1;
-      s2 = h0 - 2;
-    }
-    i32 ee[CW], qq[CW];
-    // nothing to the left of the first window column when it is not column 1 (lane 0, c == 0 only: from the second
-    // column on the running maxima hold the lane's own cells)
-    bool const have_left = s1 > -(1 << 28);
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      // (s1 + Q - (j - 1) and max(s2 + G - 2 (j - 1), s1 + Q + G - (j - 2)) of the absolute form)
-      i32 q = s1 + (Q_ + 1 - jr[c]);
-      i32 e = max(s2 + (G_ + 2 - 2 * jr[c]), q + (G_ + 1));
-      if (c == 0) {
-        q = have_left ? q : kNegInf;
-        e = have_left ? e : kNegInf;
-      }
-      i32 const m = hh[c];
-      s1 = max(s1, a1r[c]);
-      s2 = max(s2, a2r[c]);
-      ee[c] = e;
-      qq[c] = q;
-      hh[c] = max(m, max(e, q));
-    }
-    // ---- (H, E, Q) of the column to the left of this lane's first column ----
-    i32 hN = wave_shr1(hh[CW - 1], kNegInf), eN = wave_shr1(ee[CW - 1], kNegInf), qN = wave_shr1(qq[CW - 1], kNegInf);
-    if (lane == 0) {
-      hN = jb == 1 ? h0 : kNegInf;
-      eN = kNegInf;
-      qN = kNegInf;
-    }
-    // ---- decision codes ----
-    u32 cd[CW];
-    if (fast) {
-      i32 hleft = hN, eleft = eN, qleft = qN;
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        i32 const ph = H1[c];
-        i32 const a1 = F1[c] + E_, a2 = ph + G_, a3 = O1[c] + C_;
-        i32 const fv = ff[c], ov = oo[c], hm = hmv[c], h = hh[c], e = ee[c], q = qq[c];
-        i32 const b1 = eleft + E_, b2 = hleft + G_, b3 = qleft + C_;
-        bool const D = h == hm, U = h == max(fv, ov);
-        bool const eu = (h == a1) || ((h != a2) && (h == a3));
-        bool const elx = (h == b1) || ((h != b2) && (h == b3));
-        bool const lc = (b1 == e) || (b3 == q);
-        bool const us = (fv == a1) || (ov == a3);
-        u32 code = D ? 0u : (U ? 1u : 2u);
-        code |= (!D && (U ? eu : elx)) ? 4u : 0u;
-        code |= lc ? 8u : 0u;
-        code |= us ? 16u : 32u;
-        cd[c] = code;
-        hleft = h;
-        eleft = e;
-        qleft = q;
-      }
-    } else {
-      u32 elmask = 0, lcmask = 0;
-      {
-        i32 hleft = hN, eleft = eN, qleft = qN;
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          i32 const h = hh[c];
-          i32 const b1 = eleft + E_, b2 = hleft + G_, b3 = qleft + C_;
-          if ((h == b1) || ((h != b2) && (h == b3))) elmask |= 1u << c;
-          if ((b1 == ee[c]) || (b3 == qq[c])) lcmask |= 1u << c;
-          hleft = h;
-          eleft = ee[c];
-          qleft = qq[c];
-        }
-      }
-      u32 dmask = 0, umask = 0, eumask = 0, usmask = 0, uhmask = 0;
-      constexpr u32 XB = kXB<G::pe>, XM = (1u << XB) - 1u;
-      u32 xs[CW];
-#pragma unroll
-      for (int c = 0; c < CW; ++c) xs[c] = 0;
-      for (u32 x = 0; x < npe; ++x) {
-        u32 const pr = np ? pred_row(g, i, info_cur, x) : 0u;
-        i32 th[CW], tf[CW], to[CW], hd;
-        fetch(pr, th, tf, to, hd);
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          i32 const a1v = tf[c] + E_, a2v = th[c] + G_, a3v = to[c] + C_, a4v = th[c] + Q_;
-          i32 const hv = hd + ((nch == sc[c]) ? M_ : N_);
-          hd = th[c];
-          i32 const h = hh[c];
-          u32 const bit = 1u << c;
-          if (!(dmask & bit) && h == hv) {
-            dmask |= bit;
-            xs[c] |= x;
-          }
-          bool const t1v = h == a1v, t2v = h == a2v, t3v = h == a3v, t4v = h == a4v;
-          if (!(umask & bit) && (t1v || t2v || t3v || t4v)) {
-            umask |= bit;
-            xs[c] |= x << XB;
-            if (t1v || (!t2v && t3v)) eumask |= bit;
-          }
-          if (np) {
-            if (!(usmask & bit) && ((ff[c] == a1v) || (oo[c] == a3v))) {
-              usmask |= bit;
-              xs[c] |= x << (2 * XB);
-            }
-            if (!(uhmask & bit) && ((ff[c] == a2v) || (oo[c] == a4v))) {
-              uhmask |= bit;
-              xs[c] |= x << (3 * XB);
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        u32 const bit = 1u << c;
-        bool const D = dmask & bit, U = umask & bit;
-        u32 code = D ? 0u : (U ? 1u : 2u);
-        code |= (!D && (U ? ((eumask & bit) != 0) : ((elmask & bit) != 0))) ? 4u : 0u;
-        code |= (lcmask & bit) ? 8u : 0u;
-        bool const us = usmask & bit, uh = uhmask & bit;
-        code |= us ? 16u : (uh ? 32u : 0u);
-        code |= (D ? (xs[c] & XM) : (U ? ((xs[c] >> XB) & XM) : 0u)) << 6;
-        code |= (us ? ((xs[c] >> (2 * XB)) & XM) : (uh ? ((xs[c] >> (3 * XB)) & XM) : 0u)) << (6 + XB);
-        cd[c] = code;
-      }
-    }
-    // right exit of this row: the last window column when the haplotype goes on beyond it
-    if (lane == 63 && jb + CW - 1 < L) edge = max(edge, hh[CW - 1]);
-    {
-      u8* const cp = reinterpret_cast<u8*>(codes) + static_cast<size_t>(i) * BW + static_cast<u32>(CW) * lane;
-      store_code_bytes<CW>(cp, cd, 0);
-      if (!fast) store_code_bytes<CW>(cp + plane, cd, 6);
-    }
-    if (store) {
-      u32 const slot = g.rowslot[i];
-      i32* rb = rows + static_cast<size_t>(slot) * 3 * w_stride + static_cast<u32>(CW) * lane;
-      if constexpr (CW == 4) {
-        *reinterpret_cast<int4*>(rb) = make_int4(hh[0], hh[1], hh[2], hh[3]);
-        *reinterpret_cast<int4*>(rb + w_stride) = make_int4(ff[0], ff[1], ff[2], ff[3]);
-        *reinterpret_cast<int4*>(rb + 2 * static_cast<size_t>(w_stride)) = make_int4(oo[0], oo[1], oo[2], oo[3]);
-      } else if constexpr (CW == 2) {
-        *reinterpret_cast<int2*>(rb) = make_int2(hh[0], hh[1]);
-        *reinterpret_cast<int2*>(rb + w_stride) = make_int2(ff[0], ff[1]);
-        *reinterpret_cast<int2*>(rb + 2 * static_cast<size_t>(w_stride)) = make_int2(oo[0], oo[1]);
-      } else {
-        rb[0] = hh[0];
-        rb[w_stride] = ff[0];
-        rb[2 * static_cast<size_t>(w_stride)] = oo[0];
-      }
-      __threadfence_block();  // other lanes read it back (lane offsets differ between windows)
-    }
-    if (L >= j0 && L < j0 + BW && static_cast<u32>(lane) == (L - j0) / CW) {
-      u32 const cL = (L - j0) % CW;
-      i32 v = hh[0];
-#pragma unroll
-      for (int c = 1; c < CW; ++c) v = (static_cast<u32>(c) == cL) ? hh[c] : v;
-      hlast[i] = v;
-    } else if (lane == 0 && !(L >= j0 && L < j0 + BW)) {
-      hlast[i] = kNegInf;
-    }
-    // row i takes the place of row i - 2
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      H2[c] = hh[c];
-      F2[c] = ff[c];
-      O2[c] = oo[c];
-    }
-  };
-  for (u32 i = 1; i <= V; i += 2) {
-    row(i, HA, FA, OA, HB, FB, OB);
-    if (i + 1 <= V) row(i + 1, HB, FB, OB, HA, FA, OA);
-  }
-  for (int off = 32; off > 0; off >>= 1) edge = max(edge, __shfl_xor(edge, off));
-  if (lane == 0) *edge_out = edge;
-}
-
-// ---- the lean banded fill: same cells, same codes as poa_fill_band, a quarter of the instructions ----
-// The row loop of poa_fill_band costs ~500 instructions a row whatever its width: half of them scalar -- execution-mask
-// bookkeeping for per-lane conditions, uniform branches for rows that might store / slide / hold column 0 / have several
-// predecessors -- and a lone wavefront issues one instruction every 4-5 cycles, so the instruction COUNT is the fill's
-// latency.  Here every row that is ordinary takes a straight-line path (RI_LEAN, decided once per alignment by
-// band_flags in k_msa): a single predecessor = the previous rank (FAST), not read back later (no RI_STORE), not a sink
-// (no hlast), a window that does not touch column 0 and sits where the previous row's sits or one lane to its right.
-// 97 % of the rows of a haplotype graph.  The other rows take row_gen: poa_fill_band's row without the second
-// register row (a predecessor that is not the previous rank comes from the row store: k_msa marks every such row).
+// A lone wavefront issues one instruction every 4-5 cycles, so the instruction COUNT of a row is the fill's latency,
+// and scalar work -- execution-mask bookkeeping for per-lane conditions, uniform branches for rows that might store /
+// slide / hold column 0 / have several predecessors -- counts like vector work.  So every row that is ordinary takes a
+// straight-line path (RI_LEAN, decided once per alignment by band_flags in msa_window): a single predecessor = the previous
+// rank (FAST), not read back later (no RI_STORE), not a sink (no hlast), a window that sits where the previous row's sits
+// or one lane to its right (or starts at column 1 and does not slide).  97 % of the rows of a haplotype graph.
+// The other rows take row_gen: any number of predecessors, any slide, column 0, stores and sinks, with per-lane
+// branches.  Both keep ONE register row, the previous rank's; a predecessor that is not the previous rank comes from the
+// row store (msa_window marks every such row RI_STORE).  The straight-line path has
 //  * no per-lane branches: lane conditions are constant masks (v_cndmask), entering lanes are written with v_writelane;
-//  * one scalar load per row (the descriptor of the next row) instead of three;
+//  * one scalar load per row (the descriptor of the next row; row_gen also reads the row's depth and window origin);
 //  * decision codes from SIGN BITS: a FAST row's code only depends on which argument wins each maximum
 //        fA = a1 >= a2, oA = a3 >= a4, FO = fv >= ov, eB = b1 >= b2, qB = b3 >= b4, EQ = e >= q, D = h == hm, U = h == hV
 //    (poa_fill's fast path shows that SPOA's ordered equality tests collapse to these; every test is the sign of a
 //    difference, h - hm and h - hV being >= 0), so eight differences are shifted into one register with v_alignbit and
-//    the 6-bit code is read from a 256-byte table in LDS (one bank per dword: conflict-free): ~19 instead of ~35
-//    instructions per cell.  The one cell without a left neighbour (lane 0, first column) gets neighbour values that
-//    make eB = qB = false, which is what the equality tests give there (lc = 0); nothing else reads them.
+//    the 6-bit code is read from a 256-byte table in LDS (one bank per dword: conflict-free): ~19 instructions
+//    per cell (row_gen's ordered tests: ~35).  The one cell without a left neighbour (lane 0, first column) gets
+//    neighbour values that make eB = qB = false, which is what the equality tests give there (lc = 0); nothing else
+//    reads them.
 __device__ __forceinline__ u32 lean_code_of(u32 idx) {  // idx bits, 1 = "strictly less": [7] FO [6] fA [5] oA [4] D [3] U [2] EQ [1] eB [0] qB
   bool const FO = !(idx & 128u), fA = !(idx & 64u), oA = !(idx & 32u), D = !(idx & 16u), U = !(idx & 8u), EQ = !(idx & 4u),
              eB = !(idx & 2u), qB = !(idx & 1u);
@@ -1583,7 +1152,7 @@ __device__ void poa_fill_lean(G const& g, u32 const w_stride, size_t const plane
     }
   };
 
-  // ---- every other row: poa_fill_band's row with one register row ----
+  // ---- every other row: any predecessors (previous rank from registers, others from the row store), any slide ----
   auto row_gen = [&](u32 const i, u32 const info) __attribute__((always_inline)) {
     u32 const nch = info & 0xFFu, np = ri_np<G::pe>(info);
     bool const fast = info & RI_FAST, store = info & RI_STORE;
@@ -2634,7 +2203,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
           }
         }
         for (u32 x = 0; x < np; ++x)
-          if (pr[x] + 1 != i) g.rowslot[pr[x]] = 1;  // (poa_fill / poa_fill_band still take rank - 2 from registers)
+          if (pr[x] + 1 != i) g.rowslot[pr[x]] = 1;  // (the band fill keeps rank - 1 in registers only; poa_fill takes rank - 2 from registers too)
         g.rowinfo[i] = info;
         g.rowj0[i] = band_j0(g.npos[node], L, ST.band ? ST.band : 4u);
       }
@@ -2717,7 +2286,7 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
       }
       }  // !rh
       // Tiers: the narrow band first (ws.tier0: 64 or 128 columns), then 256 columns, then the full row-synchronous
-      // fill.  A band is exact when its certificate holds (see poa_fill_band) and the traceback stays inside it; a
+      // fill.  A band is exact when its certificate holds (see poa_fill_lean) and the traceback stays inside it; a
       // tier that fails hands the alignment to the next one -- through k_msa_band again while the batch is in split
       // rounds, inside this kernel (wave 0) in the last launch.
       bool filled = rh && ST.filled;  // k_msa_band has filled tier ST.band between the two launches
@@ -2736,14 +2305,9 @@ __device__ __forceinline__ u32 msa_window(MsaArgs const& A, int const lw, bool c
           }
           if (tier) {
             if (tid == 0) ST.band_fail = 0;
-            if (wave == 0) {
-              if (ws.lean)
-                poa_fill_lean<static_cast<int>(kTierIn)>(g, ws.band_stride, ws.code_cells, codes, rows, hlast, V, L, lane, seq,
-                                                         ST.edge0, g.aln.off, &ST.edge_max);
-              else
-                poa_fill_band<static_cast<int>(kTierIn)>(g, ws.band_stride, ws.code_cells, codes, rows, hlast, V, L, lane, seq,
-                                                         &ST.edge_max);
-            }
+            if (wave == 0)
+              poa_fill_lean<static_cast<int>(kTierIn)>(g, ws.band_stride, ws.code_cells, codes, rows, hlast, V, L, lane, seq,
+                                                       ST.edge0, g.aln.off, &ST.edge_max);
           } else {
             if (cw == 4) {
               poa_fill<4>(g, ws, fcodes, frows, hlast, V, L, tid, seq);
@@ -3308,7 +2872,7 @@ struct DescView {
 // (host-counted rounds) and the F job of the persistent kernel k_poa.  Nothing of the window is staged in LDS -- the state
 // block's few fields and the row descriptors come straight from the image in HBM -- so any wavefront of any workgroup can
 // run it; lut_off = 256 bytes of LDS of the wavefront's own for poa_fill_lean's code table.
-template <bool LEAN, int PE>
+template <int PE>
 __device__ __forceinline__ bool band_job(MsaArgs const& A, int const lw, int const lane, u32 const lut_off) {
   int const w = A.win0 + lw;
   ma_params_t const& P = A.prm;
@@ -3343,10 +2907,7 @@ __device__ __forceinline__ bool band_job(MsaArgs const& A, int const lw, int con
   u32 const tier = __builtin_amdgcn_readfirstlane(pst->band);
   auto const fill = [&](auto cw) {
     constexpr int CW = decltype(cw)::value;
-    if constexpr (LEAN)
-      poa_fill_lean<CW>(g, ws.band_stride, ws.code_cells, codes, rows, hlast, V, L, lane, seq, edge0, lut_off, &pst->edge_max);
-    else
-      poa_fill_band<CW>(g, ws.band_stride, ws.code_cells, codes, rows, hlast, V, L, lane, seq, &pst->edge_max);
+    poa_fill_lean<CW>(g, ws.band_stride, ws.code_cells, codes, rows, hlast, V, L, lane, seq, edge0, lut_off, &pst->edge_max);
   };
   if (tier == 1) fill(std::integral_constant<int, 1>{});
   else if (tier == 2) fill(std::integral_constant<int, 2>{});
@@ -3362,11 +2923,11 @@ __device__ __forceinline__ bool band_job(MsaArgs const& A, int const lw, int con
   return true;
 }
 
-template <bool LEAN, int PE>
+template <int PE>
 __global__ __launch_bounds__(64, 4) void k_msa_band(MsaArgs A) {
   int const lw = blockIdx.x;
   if (poa_window_skipped(A, A.win0 + lw)) return;
-  (void)band_job<LEAN, PE>(A, lw, static_cast<int>(threadIdx.x), 16u);
+  (void)band_job<PE>(A, lw, static_cast<int>(threadIdx.x), 16u);
 }
 
 // ---- the persistent POA kernel: device-side scheduling instead of host-counted rounds (round 6) ----------------------------
@@ -3564,7 +3125,7 @@ __global__ __launch_bounds__(kT, LAB32 ? 1 : 2) void k_poa(MsaArgs A, PoaSched* 
       if (static_cast<u32>(wave) < cnt) {
         int const lw = static_cast<int>(__builtin_amdgcn_readfirstlane(sh_job[2 + wave]));
         poa_acquire(dev_scope);  // the image another workgroup saved
-        (void)band_job<true, 4>(A, lw, lane, static_cast<u32>(wave) * 256u);
+        (void)band_job<4>(A, lw, lane, static_cast<u32>(wave) * 256u);
         poa_release(dev_scope);  // codes, stored rows, last column, edge maximum, the image's `filled`
         if (lane == 0) q_push(&D->g_tail, gq, qmask, static_cast<u32>(lw));
       }
@@ -3724,8 +3285,52 @@ int launch_msa(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var
   }
   return rc;
 }
+// The POA's switches.  Read once per call and handed to every pass of it -- per call, not per
+// context: the tests switch routes inside one process.
+struct PoaEnv {
+  int band_mode;    // MA_POA_BAND (default 2): see launch_msa_pass
+  u32 no_direct;    // MA_POA_NO_DIRECT
+  u32 raw_cap;      // MA_POA_RAW_CAP (0: the kernel's own)
+  u32 tier0;        // MA_POA_TIER0: columns per lane of the first band tier, 1 / 2 / 4
+  u32 min_pending;  // MA_POA_MIN_PENDING (default 256)
+  bool sched;       // MA_POA_SCHED (default 1): the persistent kernel where the pass can take it
+  int wgs_per_cu;   // MA_POA_WGS_PER_CU: k_poa workgroups per CU at most (default 2: what a CU holds)
+  u32 xcd_local;    // MA_POA_XCD (default 1)
+  bool has_ws_gb;   // MA_WS_GB: the stage's memory budget in GB (default: the context's share)
+  int ws_gb;
+  bool verbose;     // MA_VERBOSE
+};
+static PoaEnv read_poa_env() {
+  PoaEnv e{};
+  const char* s;
+  e.band_mode = (s = getenv("MA_POA_BAND")) ? atoi(s) : 2;
+  e.no_direct = getenv("MA_POA_NO_DIRECT") ? 1u : 0u;
+  e.raw_cap = (s = getenv("MA_POA_RAW_CAP")) ? static_cast<u32>(atoi(s)) : 0u;
+  int const t0 = (s = getenv("MA_POA_TIER0")) ? atoi(s) : static_cast<int>(kTierIn);
+  e.tier0 = (t0 == 1 || t0 == 2) ? static_cast<u32>(t0) : 4u;
+  e.min_pending = (s = getenv("MA_POA_MIN_PENDING")) ? static_cast<u32>(atoi(s)) : 256u;
+  e.sched = !((s = getenv("MA_POA_SCHED")) && atoi(s) == 0);
+  e.wgs_per_cu = (s = getenv("MA_POA_WGS_PER_CU")) ? atoi(s) : 2;
+  e.xcd_local = ((s = getenv("MA_POA_XCD")) && atoi(s) == 0) ? 0u : 1u;
+  e.has_ws_gb = (s = getenv("MA_WS_GB")) != nullptr;
+  e.ws_gb = s ? atoi(s) : 0;
+  e.verbose = getenv("MA_VERBOSE") != nullptr;
+  return e;
+}
+
+// The k_msa of a pass: label masks of 16 or 32 bits, four or eight slots per node, the column tier by the longest haplotype.
+// (poa_retry_max_hap_len(*, 8) < 2048: with eight slots the widest column tier is never needed, and not built)
+template <bool X>  // X: the exporting kernels (ma_msa_graph_batch)
+static auto pick_k_msa(u32 lab32, u32 pe, u32 max_len) {
+  auto kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 4, X> : (max_len <= 2048 ? k_msa<8, true, 4, X> : k_msa<16, true, 4, X>))
+                    : (max_len <= 1024 ? k_msa<4, false, 4, X> : (max_len <= 2048 ? k_msa<8, false, 4, X> : k_msa<16, false, 4, X>));
+  if (pe == 8)
+    kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 8, X> : k_msa<8, true, 8, X>) : (max_len <= 1024 ? k_msa<4, false, 8, X> : k_msa<8, false, 8, X>);
+  return kern;
+}
+
 static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o, u32 max_len, u32 rounds,
-                           u32 lab32, u32 pass, const u32 (&len_caps)[3], u8* cause);
+                           u32 lab32, u32 pass, const u32 (&len_caps)[3], u8* cause, PoaEnv const& env);
 static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o) {
   int const n = b.n_windows;
   for (auto& c : ctx->poa_retry_counts) c = 0;
@@ -3739,12 +3344,13 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
     ma_set_err(ctx, "ma_msa_batch: max_hap_len > 4096 not supported (256 lanes x 16 columns)");
     return MA_ERR_PARAM;
   }
+  PoaEnv const env = read_poa_env();
   // longest haplotype of the batch decides the DP width and the LDS graph capacity (one small D2H)
   u32 got[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   u32 const cap16 = poa_max_hap_len(0u), cap32 = poa_max_hap_len(1u);
   if (ctx->poa_all32 < 0) {  // once per context: the switch, and the bound under MA_VERBOSE
     ctx->poa_all32 = getenv("MA_POA_FORCE_LAB32") ? 1 : 0;  // tests: every window through LAB32
-    if (getenv("MA_VERBOSE"))
+    if (env.verbose)
       fprintf(stderr, "[microasm] msa: longest haplotype one LDS block holds: %u bases (%u in the LAB32 kernels)\n", cap16, cap32);
   }
   bool const all32 = ctx->poa_all32 == 1;
@@ -3774,13 +3380,13 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
     MA_HIP(ctx, hipMemsetAsync(ctx->poa_cause.p, 0, 64 + static_cast<size_t>(n), ctx->stream));
   }
   if (all32) {
-    MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u, caps, cause));
+    MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 1u, 0u, caps, cause, env));
   } else {
     // The reference has no cap on the haplotypes of a component (cbdg/graph.cpp:846-924, caller/msa_builder.cpp:29-42); the
     // engine's is the caller's max_haps <= 32.  Components of up to 16 haplotypes take the common kernels (16-bit label masks,
     // two workgroups per CU); a window with a wider component takes the LAB32 kernels in a pass of its own.
-    MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 0u, any_wide ? 1u : 0u, caps, cause));
-    if (any_wide) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, std::max(got[3], 16u), rounds, 1u, 2u, caps, cause));
+    MA_TRY_RC(launch_msa_pass(ctx, b, a, o, got[0], rounds, 0u, any_wide ? 1u : 0u, caps, cause, env));
+    if (any_wide) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, std::max(got[3], 16u), rounds, 1u, 2u, caps, cause, env));
   }
   if (!cause) return MA_OK;
   static RetryCaps const rcaps{{poa_retry_max_hap_len(0u, 8u), poa_retry_max_hap_len(1u, 8u), poa_retry_max_hap_len(0u, 4u), poa_retry_max_hap_len(1u, 4u)}};
@@ -3799,7 +3405,7 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
   // the width pass (eight slots per node), then the capacity pass (four, the block's LDS in nodes); each over the windows with
   // 16-bit label masks and over those that need 32
   for (u32 k = 0; k < 4; ++k)
-    if (mx[k]) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, mx[k], rrounds, k & 1u, 3u + k, caps, cause));
+    if (mx[k]) MA_TRY_RC(launch_msa_pass(ctx, b, a, o, mx[k], rrounds, k & 1u, 3u + k, caps, cause, env));
   hipLaunchKernelGGL(k_poa_retry_count, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a, n, static_cast<const u8*>(cause), rctr);
   MA_HIP(ctx, hipMemcpyAsync(marks, rctr, 16, hipMemcpyDeviceToHost, ctx->stream));
   MA_HIP(ctx, ma_stream_sync(ctx));
@@ -3808,7 +3414,7 @@ static int launch_msa_on_stream(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t
   return MA_OK;
 }
 static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ma_var_out_t& o, u32 max_len, u32 rounds,
-                           u32 const lab32, u32 const pass, const u32 (&len_caps)[3], u8* const cause) {
+                           u32 const lab32, u32 const pass, const u32 (&len_caps)[3], u8* const cause, PoaEnv const& env) {
   int const n = b.n_windows;
   ma_params_t const& P = ctx->prm;
   PoaWs ws{};
@@ -3836,21 +3442,16 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   // MA_POA_BAND: 2 (default) = 256-column banded fill in its own kernel (k_msa_band), 1 = banded fill inside k_msa,
   // 0 = full row-synchronous fill only.  Results are identical (the band is certified or redone in full).
   // (3, for tests: the persistent kernel with every alignment through the full fill -- its per-workgroup areas)
-  int const band_mode = getenv("MA_POA_BAND") ? atoi(getenv("MA_POA_BAND")) : 2;
-  ws.use_band = (band_mode != 0 && band_mode != 3) ? 1u : 0u;
-  ws.split = band_mode >= 2 ? 1u : 0u;
-  ws.no_direct = getenv("MA_POA_NO_DIRECT") ? 1u : 0u;
-  ws.raw_cap = getenv("MA_POA_RAW_CAP") ? static_cast<u32>(atoi(getenv("MA_POA_RAW_CAP"))) : 0u;
-  ws.lean = (getenv("MA_POA_LEAN") && atoi(getenv("MA_POA_LEAN")) == 0) ? 0u : 1u;
+  ws.use_band = (env.band_mode != 0 && env.band_mode != 3) ? 1u : 0u;
+  ws.split = env.band_mode >= 2 ? 1u : 0u;
+  ws.no_direct = env.no_direct;
+  ws.raw_cap = env.raw_cap;
   // first band tier: 64 (1), 128 (2) or 256 (4) columns; a tier whose certificate fails hands over to 256 columns, then
   // to the full fill.  Results do not depend on it (tested).
-  {
-    int const t0 = getenv("MA_POA_TIER0") ? atoi(getenv("MA_POA_TIER0")) : static_cast<int>(kTierIn);
-    ws.tier0 = (t0 == 1 || t0 == 2) ? static_cast<u32>(t0) : 4u;
-  }
+  ws.tier0 = env.tier0;
   // split mode: a band round is launched while at least this many windows wait for a fill; fewer finish inside k_msa
-  u32 const min_pending = getenv("MA_POA_MIN_PENDING") ? static_cast<u32>(atoi(getenv("MA_POA_MIN_PENDING"))) : 256u;
-  bool const verbose = getenv("MA_VERBOSE") != nullptr;
+  u32 const min_pending = env.min_pending;
+  bool const verbose = env.verbose;
   ws.img_words = static_cast<u32>((lds + 3) / 4);
   // A window's own areas hold what the band tiers write (at most 256 columns per row: 2.7 MB per window of 1 kb haplotypes);
   // the full fill's whole-row areas (10 MB) belong to whoever runs it -- see PoaWs.
@@ -3870,7 +3471,7 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   // (a retry pass takes the host-counted rounds: a handful of windows, and the persistent kernel is not built for eight slots)
   // (an exporting call -- ma_msa_graph_batch -- likewise: the exporting kernels are k_msa's)
   bool const exporting = ctx->px != nullptr;
-  bool const sched = !retry && !exporting && ws.split && ws.lean && !(getenv("MA_POA_SCHED") && atoi(getenv("MA_POA_SCHED")) == 0);
+  bool const sched = !retry && !exporting && ws.split && env.sched;
   ws.full_by_worker = sched ? 1u : 0u;
   // workgroups of the persistent kernel: what the chip holds at once (two per CU while the graph fits 80 KB of LDS; a lane
   // that runs beside others may be told to take one -- MA_POA_WGS_PER_CU -- and leave the other half of every CU's LDS to them)
@@ -3879,15 +3480,13 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
   }
-  int wgs_per_cu = lds > 80 * 1024 ? 1 : 2;
-  if (const char* e = getenv("MA_POA_WGS_PER_CU")) wgs_per_cu = std::max(1, std::min(wgs_per_cu, atoi(e)));
+  int const wgs_per_cu = std::max(1, std::min(lds > 80 * 1024 ? 1 : 2, env.wgs_per_cu));
   size_t const per_window = ws.code_cells * 2 + ws.row_cells * 4 + (static_cast<size_t>(pn) + 8) * 4 + img_bytes + (sched ? 0 : full_bytes);
-  (void)rounds;
   // The POA stage works in the ASSEMBLY stage's workspace: a lane runs its stages one after the other, and what the assembly
   // kernels leave there is dead once the haplotypes are in the caller's buffers (ma_asm_out_t).  One arena for both instead of
   // two that are never in use together: the assembly stage plans with twice the share it had (assemble.hip).
   size_t budget = stage_budget(0.30, ctx->ws_build.cap, size_t(24) << 30, ctx->hbm_share);
-  if (const char* e = getenv("MA_WS_GB")) budget = static_cast<size_t>(atoi(e)) << 30;
+  if (env.has_ws_gb) budget = static_cast<size_t>(env.ws_gb) << 30;
   // the persistent kernel's workgroups (each with a full-fill area of its own): what the chip holds, what the batch can use,
   // and no more than half the stage's memory
   size_t const max_workers = sched ? std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n, static_cast<size_t>(n_cu) * wgs_per_cu),
@@ -3898,19 +3497,12 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
   while (qcap < static_cast<u32>(chunk)) qcap <<= 1;
   MA_HIP(ctx, ctx->ws_build.reserve(per_window * static_cast<size_t>(chunk) + fixed_bytes + 16384 + 3 * sizeof(u32) * qcap * kPoaDoms +
                                   sizeof(PoaSched) + sizeof(u32) * qcap));
-  u32 const xcd_local = (getenv("MA_POA_XCD") && atoi(getenv("MA_POA_XCD")) == 0) ? 0u : 1u;
-  if (getenv("MA_VERBOSE"))
+  u32 const xcd_local = env.xcd_local;
+  if (verbose)
     fprintf(stderr, "[microasm] msa: %d windows, %.2f MB/window + %zu full-fill areas of %.2f MB, budget %.1f GB -> chunks of %d (pn %u, max_len %u, lds %zu)\n",
             n, per_window / 1048576.0, max_workers, full_bytes / 1048576.0, budget / 1073741824.0, chunk, pn, max_len, lds);
-  auto kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 4> : (max_len <= 2048 ? k_msa<8, true, 4> : k_msa<16, true, 4>))
-                    : (max_len <= 1024 ? k_msa<4, false, 4> : (max_len <= 2048 ? k_msa<8, false, 4> : k_msa<16, false, 4>));
-  if (pe == 8)  // (poa_retry_max_hap_len(*, 8) < 2048: the widest column tier is never needed)
-    kern = lab32 ? (max_len <= 1024 ? k_msa<4, true, 8> : k_msa<8, true, 8>) : (max_len <= 1024 ? k_msa<4, false, 8> : k_msa<8, false, 8>);
-  auto kernx = lab32 ? (max_len <= 1024 ? k_msa<4, true, 4, true> : (max_len <= 2048 ? k_msa<8, true, 4, true> : k_msa<16, true, 4, true>))
-                     : (max_len <= 1024 ? k_msa<4, false, 4, true> : (max_len <= 2048 ? k_msa<8, false, 4, true> : k_msa<16, false, 4, true>));
-  if (pe == 8)
-    kernx = lab32 ? (max_len <= 1024 ? k_msa<4, true, 8, true> : k_msa<8, true, 8, true>)
-                  : (max_len <= 1024 ? k_msa<4, false, 8, true> : k_msa<8, false, 8, true>);
+  auto const kern = pick_k_msa<false>(lab32, pe, max_len);
+  auto const kernx = pick_k_msa<true>(lab32, pe, max_len);
   MA_HIP(ctx, hipFuncSetAttribute(exporting ? reinterpret_cast<const void*>(kernx) : reinterpret_cast<const void*>(kern),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
   auto pkern = lab32 ? (max_len <= 1024 ? k_poa<4, true> : (max_len <= 2048 ? k_poa<8, true> : k_poa<16, true>))
@@ -4016,15 +3608,8 @@ static int launch_msa_pass(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, 
           break;
         }
         ctx->tic("k_msa_band");
-        auto band = [&](auto kfn) { hipLaunchKernelGGL(kfn, dim3(nwin), dim3(64), band_lds, ctx->stream, args); };
-        if (pe == 8) {
-          if (ws.lean) band(k_msa_band<true, 8>);
-          else band(k_msa_band<false, 8>);
-        } else if (ws.lean) {
-          band(k_msa_band<true, 4>);  // (first tiers, retried fills and haplotypes that start wide alike)
-        } else {
-          band(k_msa_band<false, 4>);
-        }
+        // (one launch for first tiers, retried fills and haplotypes that start wide alike)
+        hipLaunchKernelGGL(pe == 8 ? k_msa_band<8> : k_msa_band<4>, dim3(nwin), dim3(64), band_lds, ctx->stream, args);
         ctx->toc();
       }
     }

@@ -285,6 +285,61 @@ def _length_window(n, seed, kind=None, may_flag=None):
     return Window(f"length_{n}", [Comp(ref, alts)], may_flag=bool(kind) if may_flag is None else may_flag, kind=kind, truth=truth)
 
 
+# ---- rows of the banded fill that are not straight-line ----
+# poa.hip's band_flags marks a row RI_LEAN -- poa_fill_lean's straight-line body -- when it has one predecessor, the previous
+# rank, no later row reads it back, it is not a sink, and its window sits where the previous row's sits or one lane to the
+# right (or both start at column 1).  Every other row takes the any-shape body (row_gen).  One window per way out, on
+# haplotypes of 400 bases and more (shorter ones are not banded), none of them may_flag:
+#   band_store_bubbles   rows with two predecessors, the far one read back from the row store (RI_STORE): a 5-base deletion
+#                        and a 6-base insertion open two bubbles; the second and the third haplotype cross both with
+#                        substitutions within three bases of each branch point
+#   band_col0_insertion  rows that are not FAST while the window starts at column 1: two haplotypes with an insertion within
+#                        their first four bases (the second one is filled against the first one's inserted nodes)
+#   band_window_jump     a window that moves by more than a lane between two ranks.  A 40-base deletion already in the graph
+#                        is crossed by a later haplotype; the deletion alone leaves the backbone coordinate rising by one per
+#                        rank (its far end is one more two-predecessor row), so the window also holds a 40-base insertion:
+#                        its nodes count 40 coordinates on and the REF node behind them steps back by as many, 20 lanes of
+#                        the 128-column tier
+#   band_early_sink      a sink that is not the last rank: a haplotype that ends 30 bases early.  Ending early alone adds no
+#                        sink (its last node keeps the REF's edge out), so its last base is a substitution: that node has no
+#                        edge out and 30 ranks or more behind it
+#   band_to_full_fill    the 128-column tier fails, the 256-column tier fails too, the alignment ends in the full fill: a
+#                        150-base deletion with a 60-base insertion 10 bases behind it walks 150 columns off the backbone;
+#                        a second 60-base insertion keeps the haplotype within 48 bases of the REF's length, so that it
+#                        starts at the first tier
+def _band_shape_windows():
+    n, ws = 800, []
+    ref, alts = _draw_ref(6601, n, lambda r, g: [
+        [("del", 200, 5), ("ins", 500, rand_dna(g, 6)), _snv(r, 650)],
+        [_snv(r, 198), _snv(r, 206), _snv(r, 499), _snv(r, 501)],
+        [_snv(r, 197, 2), _snv(r, 207, 2), _snv(r, 498, 2), _snv(r, 502, 2)]], no_repeat=(190, 215))
+    ws.append(Window("band_store_bubbles", [Comp(ref, alts)]))
+    ref, alts = _draw_ref(6602, n, lambda r, g: [
+        [("ins", 2, rand_dna(g, 5)), _snv(r, 300), _snv(r, 600)],
+        [("ins", 3, rand_dna(g, 4)), _snv(r, 350), _snv(r, 620, 2)]], no_repeat=(0, 12))
+    ws.append(Window("band_col0_insertion", [Comp(ref, alts)]))
+    ref, alts = _draw_ref(6603, n, lambda r, g: [
+        [_snv(r, 100), ("del", 300, 40)],
+        [("ins", 500, rand_dna(g, 40)), _snv(r, 650)],
+        [_snv(r, 150, 2), _snv(r, 520, 2), _snv(r, 700, 2)]])
+    (s100, _), (ins, s650), (s150, s520, s700) = alts
+    ws.append(Window("band_window_jump", [Comp(ref, alts)], truth=[
+        _snv_truth(ref, 100, s100[2], 1), _snv_truth(ref, 150, s150[2], 3), _del_truth(ref, 300, 40, 1), _ins_truth(ref, 500, ins[2], 2),
+        _snv_truth(ref, 520, s520[2], 3), _snv_truth(ref, 650, s650[2], 2), _snv_truth(ref, 700, s700[2], 3)]))
+    ref, alts = _draw_ref(6604, n, lambda r, g: [
+        [_snv(r, 200), _snv(r, n - 31), ("del", n - 30, 30)],
+        [_snv(r, 400), _snv(r, 500, 2), _snv(r, n - 20, 2)]])
+    ws.append(Window("band_early_sink", [Comp(ref, alts)]))
+    ref, alts = _draw_ref(6605, n, lambda r, g: [
+        [("del", 300, 150), ("ins", 460, rand_dna(g, 60)), ("ins", 700, rand_dna(g, 60))],
+        [_snv(r, 100), _snv(r, 250, 2), _snv(r, 750, 2)]])
+    (_, i460, i700), (s100, s250, s750) = alts
+    ws.append(Window("band_to_full_fill", [Comp(ref, alts)], truth=[
+        _snv_truth(ref, 100, s100[2], 2), _snv_truth(ref, 250, s250[2], 2), _del_truth(ref, 300, 150, 1), _ins_truth(ref, 460, i460[2], 1),
+        _ins_truth(ref, 700, i700[2], 1), _snv_truth(ref, 750, s750[2], 2)]))
+    return ws
+
+
 def _interleave(ordinary, special):
     """every special window between two ordinary ones"""
     out, o = [], list(ordinary)
@@ -305,6 +360,8 @@ def groups():
         [_out_degree(2, 6002), _out_degree(3, 6003), _in_degree(2, 6012), _in_degree(3, 6013), _plain("degree_plain", 6020)],
         [_out_degree(4, 6004), _out_degree(5, 6005), _in_degree(4, 6014), _in_degree(5, 6015)]), routes=True))
     gs.append(Group("ring", capi.default_params(**small), [_ring(b"", 6100), _ring(b"Na", 6102), _ring(b"N", 6101)], routes=True))
+    gs.append(Group("band_shapes", capi.default_params(**small), _interleave(
+        [_plain(f"band_plain_{i}", 6610 + i) for i in range(6)], _band_shape_windows()), routes=True))
     # node headroom: the batch's longest haplotype is 1060 bases, pn <= 1060 + 256 + 7
     gs.append(Group("headroom_1k", capi.default_params(**small), _interleave(
         [_insertions("ins_2x60", 2, 6200), _snv_spread("snv_40_on_1000", 40, 6210, 1000), _plain("headroom_plain", 6220, 900)],
@@ -344,7 +401,7 @@ def groups():
     return {g.name: g for g in gs}
 
 
-ROUTE_GROUPS = tuple(n for n in ("run", "degree", "ring", "headroom_1k", "headroom_2400"))
+ROUTE_GROUPS = tuple(n for n in ("run", "degree", "ring", "band_shapes", "headroom_1k", "headroom_2400"))
 # the switches the suite already uses to force the POA's other routes (test_gpu_parity.py, test_gpu_wide_components.py)
 ROUTES = {"default": {}, "host_rounds": {"MA_POA_SCHED": "0"}, "full_fill": {"MA_POA_BAND": "0"}, "no_direct": {"MA_POA_NO_DIRECT": "1"},
           "lab32": {"MA_POA_FORCE_LAB32": "1"}, "raw_cap": {"MA_POA_RAW_CAP": "4"}}

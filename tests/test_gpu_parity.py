@@ -317,13 +317,12 @@ def test_msa_full_fill_inside_the_persistent_kernel(monkeypatch):
     assert want0["win_nvars"].sum() > 50
 
 
-@pytest.mark.parametrize("lean,raw_cap", [("0", None), ("1", "4"), ("1", "40")])
-def test_msa_parity_lean_fill_and_bubble_scratch(lean, raw_cap, monkeypatch):
-    """poa_fill_lean (default) against poa_fill_band (MA_POA_LEAN=0): same decision codes, so the same variants; and the
-    bubble walk's raw alleles in LDS (default) against the HBM route a bubble takes when an allele outgrows its LDS share
+@pytest.mark.parametrize("raw_cap", [None, "4", "40"])
+def test_msa_parity_lean_fill_and_bubble_scratch(raw_cap, monkeypatch):
+    """The banded fill (poa_fill_lean) on the default route, no switch set: the oracle's variants; and the bubble walk's
+    raw alleles in LDS (default) against the HBM route a bubble takes when an allele outgrows its LDS share
     (MA_POA_RAW_CAP = 4 / 40 bytes: every bubble / the 60-base ones move)."""
     from lancet2_amd.engine import Engine
-    monkeypatch.setenv("MA_POA_LEAN", lean)
     if raw_cap:
         monkeypatch.setenv("MA_POA_RAW_CAP", raw_cap)
     params = capi.default_params(min_k=25, max_k=25)

@@ -25,7 +25,7 @@ ANCHOR = 17
 CMP_KEYS = ("base", "rank", "col", "haps", "edges", "seq_first", "ncols", "rows", "paths")
 VAR_KEYS = tuple(capi.var_out_spec(capi.default_params(), 1))
 SWITCHES = {"full_fill": {"MA_POA_BAND": "0"}, "band_in_kernel": {"MA_POA_BAND": "1"}, "no_direct": {"MA_POA_NO_DIRECT": "1"},
-            "no_lean": {"MA_POA_LEAN": "0"}, "raw_cap": {"MA_POA_RAW_CAP": "4"}, "lab32": {"MA_POA_FORCE_LAB32": "1"}}
+            "raw_cap": {"MA_POA_RAW_CAP": "4"}, "lab32": {"MA_POA_FORCE_LAB32": "1"}}
 
 
 @lru_cache(maxsize=None)
