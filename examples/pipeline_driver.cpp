@@ -12,7 +12,9 @@
 //             (--out-graphs-dir DIR: debugging -- the batch once more through ma_assemble_graph_batch, one DOT file per component)
 //             (--out-msa-dir DIR: debugging -- the batch once more through ma_assemble_batch + ma_msa_graph_batch, a GFA and a
 //              FASTA file per component)
-//   flush     results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
+//             (--probe-variants FILE --probe-results FILE: debugging -- the batch once more through ma_assemble_probe_batch, the
+//              reference's probe_results.tsv with the columns the engine produces)
+//   flush    results -> records -> VariantStore (same CHROM+POS+REF from overlapping windows: the better covered call wins)
 //             -> everything before the next batch's first window is written, in coordinate order
 // Build (no HIP headers needed; zlib only for BAM input):
 //   g++ -std=c++17 -O2 examples/pipeline_driver.cpp -Iinclude -Llancet2_amd -lmicroasm -Wl,-rpath,$PWD/lancet2_amd
@@ -314,6 +316,37 @@ long WriteMsaFiles(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& ref, 
   return written;
 }
 
+// --probe-variants / --probe-results: the batch once more through ma_assemble_probe_batch with the truth variants whose start
+// lies in one of its windows; the lines of lancet2_amd::host::RenderProbeLines go to `out`.  Returns the number of lines
+// written, -1 when the call failed.
+long WriteProbeResults(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& ref, FlatBatch const& fb,
+                       std::vector<ProbeVariant> const& variants, FILE* out, size_t* skipped) {
+  int const n = fb.view.n_windows;
+  ProbeBatch const pb = ActivateProbes(variants, fb.windows, [&](int chrom) -> std::string const& { return ref.chroms[static_cast<size_t>(chrom)].name; });
+  *skipped += pb.skipped;
+  size_t const np = pb.id.size(), MC = static_cast<size_t>(prm.max_comps);
+  if (np == 0) return 0;
+  Outputs o;
+  o.Allocate(prm, n, false);
+  std::vector<uint32_t> rows(np * (8 + 5 * MC), 0);
+  ma_probe_out_t po{};
+  po.pb_k = rows.data(); po.pb_alt_kmers = po.pb_k + np; po.pb_in_reads = po.pb_alt_kmers + np; po.pb_lowcov1 = po.pb_in_reads + 2 * np;
+  po.pb_final = po.pb_lowcov1 + 4 * np; po.pb_hap_mask = po.pb_final + 4 * MC * np;
+  ma_probes_t const pv = pb.View();
+  if (ma_assemble_probe_batch(ctx, &fb.view, &o.asmb, &pv, &po) != MA_OK) return -1;
+  long written = 0;
+  for (int w = 0; w < n; ++w) {
+    auto const& win = fb.windows[static_cast<size_t>(w)];
+    std::string const region = ref.chroms[static_cast<size_t>(win.chrom)].name + ":" + std::to_string(win.start1) + "-" + std::to_string(win.end1);
+    for (uint32_t i = pb.win_off[static_cast<size_t>(w)]; i < pb.win_off[static_cast<size_t>(w) + 1]; ++i) {
+      std::string const lines = RenderProbeLines(prm, o.asmb, po, i, w, pb.id[i], variants[pb.id[i]], region);
+      std::fputs(lines.c_str(), out);
+      written += static_cast<long>(std::count(lines.begin(), lines.end(), '\n'));
+    }
+  }
+  return written;
+}
+
 AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed) {
   bool const bam = path.size() > 4 && path.substr(path.size() - 4) == ".bam";
 #ifdef LANCET2_AMD_WITH_ZLIB
@@ -343,7 +376,7 @@ int main(int argc, char** argv) {
   //  in force -- ADVICE r5; the flat arrays are far below 32 MiB)
   if (mallopt(M_MMAP_THRESHOLD, 32 << 20) != 1 || mallopt(M_TRIM_THRESHOLD, 1 << 30) != 1 || mallopt(M_TOP_PAD, 64 << 20) != 1)
     std::fprintf(stderr, "pipeline_driver: mallopt rejected a setting; large arrays fall back to mmap (slower, still correct)\n");
-  std::string ref_path, out_path, dump_dir, vcf_path, command_line, graphs_dir, msa_dir;
+  std::string ref_path, out_path, dump_dir, vcf_path, command_line, graphs_dir, msa_dir, probe_variants_path, probe_results_path;
   for (int i = 0; i < argc; ++i) command_line += std::string(i ? " " : "") + argv[i];
   double gc_frac = 0.41;  // --genome-gc-bias of the reference CLI: background GC of the LongdustQ null model
   std::vector<std::string> normals, tumors, regions;
@@ -382,6 +415,8 @@ int main(int argc, char** argv) {
     else if (a == "--dump") dump_dir = next();
     else if (a == "--out-graphs-dir") graphs_dir = next();  // debugging: one DOT file per assembled component (assembles twice)
     else if (a == "--out-msa-dir") msa_dir = next();  // debugging: a GFA and a FASTA file per component (assembles and aligns twice)
+    else if (a == "--probe-variants") probe_variants_path = next();  // debugging: truth variants to follow (assembles twice)
+    else if (a == "--probe-results") probe_results_path = next();    // ... and where their records go
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
     else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
@@ -404,6 +439,13 @@ int main(int argc, char** argv) {
                          "                  goes through ma_assemble_batch + ma_msa_graph_batch and DIR/msa__<chrom>_<start>_<end>__c<comp>.gfa\n"
                          "                  (the SPOA graph: a segment per node, a link per edge, a path per haplotype) and .fasta (the MSA\n"
                          "                  rows) are written for every component.  Not with --packed-reads; keep --batch-windows at a few hundred\n"
+                         "  --probe-variants FILE --probe-results FILE  a debugging mode that ASSEMBLES EVERY BATCH TWICE: FILE is the reference's\n"
+                         "                  missed_variants.txt (a header line, then tab-separated chrom, 0-based start, end, ref, alt, type, length,\n"
+                         "                  classification, raw_alt_count, ...).  A variant is followed in every window whose region holds its start\n"
+                         "                  (ma_assemble_probe_batch) and the results file gets the reference's probe_results.tsv header and one line\n"
+                         "                  per (probe, window, component) -- one with comp_id . for a window without a component: kmer_size,\n"
+                         "                  n_expected_alt_kmers, n_alt_kmers_in_reads, n_surviving_lowcov1, n_surviving_tips, hap_indices and the\n"
+                         "                  three n_last_* columns; every other result column is \".\".  Not with --packed-reads\n"
                          "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
                          "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
                          "                  all 24 FORMAT values.  Without it those six are \".\"\n"
@@ -417,6 +459,14 @@ int main(int argc, char** argv) {
   }
   if (packed_reads && !graphs_dir.empty()) {  // (the stage calls do not take the packed form: include/microasm.h)
     std::fprintf(stderr, "pipeline_driver: --out-graphs-dir needs ASCII reads (not with --packed-reads)\n");
+    return 2;
+  }
+  if (probe_variants_path.empty() != probe_results_path.empty()) {
+    std::fprintf(stderr, "pipeline_driver: --probe-variants and --probe-results go together\n");
+    return 2;
+  }
+  if (packed_reads && !probe_variants_path.empty()) {  // (likewise)
+    std::fprintf(stderr, "pipeline_driver: --probe-variants needs ASCII reads (not with --packed-reads)\n");
     return 2;
   }
   if (packed_reads && !msa_dir.empty()) {  // (likewise)
@@ -703,7 +753,20 @@ int main(int argc, char** argv) {
   });
   // ---- stage 2: engine ----
   bool const with_meta = read_meta && !vcf_path.empty();
-  size_t n_graph_files = 0, n_msa_files = 0;
+  size_t n_graph_files = 0, n_msa_files = 0, n_probe_lines = 0, n_probe_skipped = 0;
+  std::vector<ProbeVariant> probe_variants;
+  FILE* probe_out = nullptr;
+  if (!probe_variants_path.empty()) {
+    try {
+      probe_variants = LoadProbeVariants(probe_variants_path);
+    } catch (std::exception const& e) {
+      std::fprintf(stderr, "pipeline_driver: %s\n", e.what());
+      return 2;
+    }
+    probe_out = std::fopen(probe_results_path.c_str(), "w");
+    if (!probe_out) { std::perror("--probe-results"); return 4; }
+    std::fputs(kProbeResultsHeader, probe_out);
+  }
   std::thread engine([&] {
     Job j;
     while (to_engine.Pop(&j)) {
@@ -738,6 +801,15 @@ int main(int argc, char** argv) {
           j.err = std::string("--out-graphs-dir: ") + ma_last_error(ctx);
         } else {
           n_graph_files += static_cast<size_t>(nf);
+        }
+      }
+      if (j.rc == MA_OK && probe_out) {
+        long const nl = WriteProbeResults(ctx, prm, ref, *j.batch, probe_variants, probe_out, &n_probe_skipped);
+        if (nl < 0) {
+          j.rc = MA_ERR_HIP;
+          j.err = std::string("--probe-variants: ") + ma_last_error(ctx);
+        } else {
+          n_probe_lines += static_cast<size_t>(nl);
         }
       }
       if (j.rc == MA_OK && !msa_dir.empty()) {
@@ -823,6 +895,11 @@ int main(int argc, char** argv) {
                "pipeline_driver: %zu windows (%zu N-only, %zu max-k repeat, %zu inactive, %zu below anchor coverage), %zu assembled, "
                "%zu with a capacity flag, %zu records\n",
                windows.size(), n_skipped[1], n_skipped[2], n_skipped[3], n_skipped[4], n_assembled, n_flagged, n_records);
+  if (probe_out) {
+    std::fclose(probe_out);
+    std::fprintf(stderr, "pipeline_driver: %zu probe records of %zu truth variants written to %s (%zu activations skipped: an allele past its window or the call's limits)\n",
+                 n_probe_lines, probe_variants.size(), probe_results_path.c_str(), n_probe_skipped);
+  }
   if (!graphs_dir.empty()) std::fprintf(stderr, "pipeline_driver: %zu component graphs written to %s\n", n_graph_files, graphs_dir.c_str());
   if (!msa_dir.empty()) std::fprintf(stderr, "pipeline_driver: %zu MSA files written to %s\n", n_msa_files, msa_dir.c_str());
   double const wall = secs(Clock::now() - t_start);

@@ -22,6 +22,8 @@
  *   ma_process_cx_batch    <- ma_process_meta_batch + the annotation of ma_annotate_batch as a stage of the chain, where
  *                             VariantBuilder::ExtractVariants has it (core/variant_builder.cpp:157-160): the whole per-window
  *                             body in one call
+ *   ma_assemble_probe_batch <- ma_assemble_batch + the --probe-variants diagnostic: each truth allele followed through the
+ *                             window's reads, raw graph, pruned graph and haplotypes (cbdg/probe_tracker.cpp)
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -460,6 +462,76 @@ int ma_assemble_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out
  * after an earlier pass had reported it with components counts once per pass that wrote its rows.
  * Returns the number of entries written. */
 int ma_last_graph_export(ma_ctx_t* ctx, unsigned long long* out, int cap);
+
+/* ---- probe variants: where in a window's assembly a known allele was lost ---------------------------------------------- */
+/* The reference's --probe-variants diagnostic (cbdg/probe_index.{h,cpp}, cbdg/probe_tracker.{h,cpp}, cbdg/
+ * probe_results_writer.cpp, core/probe_diagnostics.h) for a batch: every truth allele is followed through four checkpoints --
+ * its ALT k-mers in the window's reads, after the first low-coverage pass, in the pruned graph, and in the haplotypes.
+ *
+ * A PROBE belongs to one window: pos = window-relative 0-based offset of the first REF base (pos < window length), ref_len
+ * (pos + ref_len <= window length) and an ALT string; the REF bases are the window's own.  A truth variant that lies in two
+ * overlapping windows is two probes.  At most 256 probes per window, ref_len and the ALT at most 256 bases (MA_ERR_PARAM
+ * beyond); a probe outside its window is MA_ERR_ARG -- checked on the host with MA_MEM_HOST and by the kernel for device
+ * pointers, where the bad probe's row is zeroed, never read out of bounds.  (alt_pool itself cannot be checked on the device:
+ * probe_alt_off + probe_alt_len must lie inside it.)
+ * k is win_k[w] as the call returns it: the last rung the window attempted.  A window with win_k == 0 has all-zero rows.
+ * CONTEXTS (probe_tracker.cpp:62-96, ComputeFlankRange / BuildAltContext): with f = k - 1, a = max(0, pos - f),
+ * e = min(len, pos + ref_len + f), the REF context is ref[a:e] and the ALT context ref[a:pos] + ALT + ref[pos + ref_len:e].
+ * EQUALITY of k-mers: two k-mers are equal if one equals the other or its reverse complement (the canonical form of
+ * DESIGN.md section 2).  A k-mer that holds any byte other than A C G T equals nothing, is never ALT-unique and never
+ * counted -- a stated deviation: the reference hashes such k-mers (kmer.cpp:17-28).  Equality is decided on the letters.
+ * ALT-UNIQUE k-mers: the k-mers of the ALT context, in order, that equal no k-mer of the REF context (probe_tracker.cpp:
+ * 99-121, :273-285); offset j = 0, 1, ... numbers them in context order, and n_alt is their number.  A k-mer that occurs at two
+ * offsets counts at both, as the reference's two tags on one node do.  Stated deviation in the numbering: the reference
+ * numbers only the ALT-unique k-mers that are in the graph at build time (GenerateAndTag, :279-283); this call numbers all of
+ * them, so that "edge" means the true first and last ALT-unique k-mer.
+ * A PROFILE of a set of surviving offsets (CountSurvivingKmers, probe_tracker.cpp:602-654) is four numbers: count; edge =
+ * survivors at offset 0 or n_alt - 1; interior = the rest; gaps = adjacent survivors whose offsets differ by more than 1. */
+typedef struct ma_probes {
+  const uint32_t* probe_win_off;  /* [n_windows + 1]: window w owns probes [probe_win_off[w], probe_win_off[w + 1]) */
+  const uint32_t* probe_pos;      /* per probe */
+  const uint32_t* probe_ref_len;
+  const uint32_t* probe_alt_off;  /* into alt_pool */
+  const uint32_t* probe_alt_len;
+  const uint8_t* alt_pool;        /* ASCII */
+} ma_probes_t;
+/* All arrays are indexed by probe and all are required.  Rows of windows with win_k == 0 are zero.
+ *   pb_k         the k the row was computed at
+ *   pb_alt_kmers n_alt
+ *   pb_in_reads  [0] occurrences of ALT-unique k-mers over ALL reads of the window, whatever their flags, per occurrence and
+ *                per offset (CountInReads, probe_tracker.cpp:299-330); [1] the reads that hold at least one
+ *   pb_lowcov1   the profile over the raw graph after BuildGraph and RemoveLowCovNodes(0), window-wide: the reference's
+ *                pruned_at_lowcov1 with its component-0 sentinel -- what the build pass hands to the clean pass
+ *   pb_final     per component that has a row in comp_*: the profile over the alive nodes of the component in the state
+ *                ma_graph_out_t shows -- the reference's pruned_at_tips.  A k-mer survives iff it occurs in the sequence of an
+ *                alive node of that component: merges lose nothing, removals lose whole nodes
+ *   pb_hap_mask  per component row: bit h is set iff haplotype h of the component (0 = REF) contains the ALT context as a
+ *                substring, forward only, byte for byte (CheckPaths, probe_tracker.cpp:472-496)
+ * Rows are those of the last pass that attempted the window: a window that a capacity retry pass assembles again has its rows
+ * cleared first, as the graph export does.  For a window the call leaves MA_W_TABLE_OVERFLOW pb_lowcov1 and pb_final are
+ * unspecified, as the graph export is: the capacity may have run out in the build pass (no complete raw graph: zeros) or in
+ * the walk search, after some components were reported and others not.
+ * NOT produced: counts inside the fused clean kernels (the second low-coverage pass, the compression
+ * stages) and before the first low-coverage pass, one record per rung, the anchor / cycle / complexity flags, the MSA and
+ * genotyper attribution, the chained and multi-lane calls. */
+typedef struct ma_probe_out {
+  uint32_t* pb_k;          /* [n_probes] */
+  uint32_t* pb_alt_kmers;  /* [n_probes] */
+  uint32_t* pb_in_reads;   /* [n_probes * 2] */
+  uint32_t* pb_lowcov1;    /* [n_probes * 4] count, edge, interior, gaps */
+  uint32_t* pb_final;      /* [n_probes * max_comps * 4] */
+  uint32_t* pb_hap_mask;   /* [n_probes * max_comps] */
+} ma_probe_out_t;
+/* ma_assemble_batch + one row per probe.  probes == NULL or probe_out == NULL IS ma_assemble_batch: the same kernels, nothing
+ * allocated.  Otherwise every array of both structs is required, and so are win_k, win_ncomp, comp_hap0, comp_nhaps, hap_len
+ * and hap_bases of `out` (MA_ERR_ARG).  Both memory spaces: with MA_MEM_DEVICE the arrays of both structs are device pointers
+ * (the structs themselves are always in host memory).  The assembly outputs are byte for byte those of ma_assemble_batch on
+ * the same batch.  Like ma_assemble_graph_batch the call climbs the k ladder rung by rung and takes the clean kernels that
+ * leave marks; three kernels of its own do the matching (probe.hip): k_probe_raw between the build and the clean pass of
+ * every attempt, k_probe_nodes where k_graph_export runs, k_probe_reads once at the end.  Single lane, like every stage call.
+ * After an error return the probe rows are unspecified (bad probes' rows are zero). */
+int ma_assemble_probe_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* out, const ma_probes_t* probes,
+                            const ma_probe_out_t* probe_out);
 
 /* ---- POA export: the SPOA graph and the MSA rows of every component --------------------------------------------------- */
 /* What the reference writes per component with --out-graphs-tgz beside the DOT file (core/variant_builder.cpp:47-70,

@@ -209,6 +209,45 @@ def make_graph_struct(arrays, max_nodes, max_edges, max_seq_bytes):
     return s
 
 
+MA_ERR_ARG, MA_ERR_PARAM = -1, -5
+PROBE_MAX_PER_WINDOW, PROBE_MAX_ALLELE = 256, 256
+PROBE_DTYPES = dict(probe_win_off=np.uint32, probe_pos=np.uint32, probe_ref_len=np.uint32, probe_alt_off=np.uint32,
+                    probe_alt_len=np.uint32, alt_pool=np.uint8)
+
+
+class Probes(C.Structure):
+    """ma_probes_t: six arrays, all required"""
+    _fields_ = [(n, C.c_void_p) for n in PROBE_DTYPES]
+
+
+class ProbeOut(C.Structure):
+    """ma_probe_out_t: six arrays indexed by probe, all required"""
+    _fields_ = [(n, C.c_void_p) for n in ("pb_k", "pb_alt_kmers", "pb_in_reads", "pb_lowcov1", "pb_final", "pb_hap_mask")]
+
+
+def probe_out_spec(p, n_probes):
+    """arrays of ma_probe_out_t for n_probes probes (ma_assemble_probe_batch); profiles are count, edge, interior, gaps"""
+    P, MC = n_probes, p.max_comps
+    return dict(pb_k=(np.uint32, P), pb_alt_kmers=(np.uint32, P), pb_in_reads=(np.uint32, P * 2), pb_lowcov1=(np.uint32, P * 4),
+                pb_final=(np.uint32, P * MC * 4), pb_hap_mask=(np.uint32, P * MC))
+
+
+def pack_probes(per_window):
+    """ma_probes_t's arrays from one list of (pos, ref_len, alt bytes) per window, in window order"""
+    win_off, pos, ref_len, alt_off, alt_len, pool = [0], [], [], [], [], bytearray()
+    for probes in per_window:
+        for p, rl, alt in probes:
+            pos.append(p)
+            ref_len.append(rl)
+            alt_off.append(len(pool))
+            alt_len.append(len(alt))
+            pool += bytes(alt)
+        win_off.append(len(pos))
+    u32 = lambda v: np.asarray(v, dtype=np.uint32)  # noqa: E731
+    return dict(probe_win_off=u32(win_off), probe_pos=u32(pos), probe_ref_len=u32(ref_len), probe_alt_off=u32(alt_off),
+                probe_alt_len=u32(alt_len), alt_pool=np.frombuffer(bytes(pool) + b"\0", dtype=np.uint8).copy())
+
+
 MA_P_NODE_OVERFLOW, MA_P_EDGE_OVERFLOW, MA_P_COL_OVERFLOW = 1, 2, 4
 POA_EXPORT_KEYS = ("first", "lab32", "retry_width", "retry_capacity")  # ma_last_poa_export: windows exported per kind of pass
 POA_OUT_CAPS = ("max_pnodes", "max_pedges", "max_cols")

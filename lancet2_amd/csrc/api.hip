@@ -114,6 +114,13 @@ std::vector<OutField> graph_fields(const ma_params_t& p, int n, const ma_graph_o
           {off_of(&ma_graph_out_t::seq_pool), N * MS}};
 }
 
+std::vector<OutField> probe_fields(const ma_params_t& p, size_t n_probes) {
+  size_t const P = n_probes, MC = p.max_comps;
+  return {{off_of(&ma_probe_out_t::pb_k), 4 * P}, {off_of(&ma_probe_out_t::pb_alt_kmers), 4 * P},
+          {off_of(&ma_probe_out_t::pb_in_reads), 4 * P * 2}, {off_of(&ma_probe_out_t::pb_lowcov1), 4 * P * 4},
+          {off_of(&ma_probe_out_t::pb_final), 4 * P * MC * 4}, {off_of(&ma_probe_out_t::pb_hap_mask), 4 * P * MC}};
+}
+
 std::vector<OutField> poa_fields(const ma_params_t& p, int n, const ma_poa_out_t& x) {
   size_t const N = n, MC = p.max_comps, MH = p.max_haps, MN = x.max_pnodes, ME = x.max_pedges, MX = x.max_cols;
   return {{off_of(&ma_poa_out_t::win_pstatus), 4 * N}, {off_of(&ma_poa_out_t::win_npnodes), 4 * N},
@@ -1328,6 +1335,8 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->ws_unpack.release();
   ctx->ws_sort.release();
   ctx->gx_mark.release(); ctx->gx_routes.release(); ctx->px_ctr.release();
+  for (auto& bf : ctx->pb_in) bf.release();
+  ctx->pb_err.release();
   ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
@@ -1554,6 +1563,91 @@ int ma_assemble_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out
   MA_TRY(a.download(ctx));
   MA_TRY(g.download(ctx));
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
+  return MA_OK;
+}
+
+int ma_assemble_probe_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* out, const ma_probes_t* pr,
+                            const ma_probe_out_t* po) {
+  if (!pr || !po) return ma_assemble_batch(ctx, b, out);  // the plain call: the same kernels, nothing allocated
+  MA_BEGIN(ctx);
+  if (!out || !b || b->n_windows < 0) return MA_ERR_ARG;
+  if (!pr->probe_win_off || !pr->probe_pos || !pr->probe_ref_len || !pr->probe_alt_off || !pr->probe_alt_len || !pr->alt_pool ||
+      !po->pb_k || !po->pb_alt_kmers || !po->pb_in_reads || !po->pb_lowcov1 || !po->pb_final || !po->pb_hap_mask)
+    return MA_ERR_ARG;
+  // (k_probe_reads reads these on the device)
+  if (!out->win_k || !out->win_ncomp || !out->comp_hap0 || !out->comp_nhaps || !out->hap_len || !out->hap_bases) return MA_ERR_ARG;
+  size_t const n = static_cast<size_t>(b->n_windows);
+  ProbeDev pd{};
+  pd.max_comps = static_cast<u32>(ctx->prm.max_comps);
+  size_t n_probes = 0;
+  if (ctx->memspace == MA_MEM_HOST) {
+    // the probes are checked here; with device pointers k_probe_reads checks them
+    if (!b->ref_off) return MA_ERR_ARG;
+    size_t pool_bytes = 0;
+    for (size_t w = 0; w < n; ++w) {
+      u32 const p0 = pr->probe_win_off[w], p1 = pr->probe_win_off[w + 1];
+      if (p1 < p0) return MA_ERR_ARG;
+      if (p1 - p0 > 256u) return MA_ERR_PARAM;
+      u32 const len = b->ref_off[w + 1] - b->ref_off[w];
+      for (u32 p = p0; p < p1; ++p) {
+        if (pr->probe_pos[p] >= len || pr->probe_ref_len[p] > len - pr->probe_pos[p]) return MA_ERR_ARG;
+        if (pr->probe_alt_len[p] > 256u || pr->probe_ref_len[p] > 256u) return MA_ERR_PARAM;
+        pool_bytes = std::max(pool_bytes, static_cast<size_t>(pr->probe_alt_off[p]) + pr->probe_alt_len[p]);
+      }
+    }
+    n_probes = pr->probe_win_off[n];
+    struct Item { const void* src; size_t bytes; const void** dst; };
+    Item const items[6] = {{pr->probe_win_off, 4 * (n + 1), reinterpret_cast<const void**>(&pd.in.probe_win_off)},
+                           {pr->probe_pos, 4 * n_probes, reinterpret_cast<const void**>(&pd.in.probe_pos)},
+                           {pr->probe_ref_len, 4 * n_probes, reinterpret_cast<const void**>(&pd.in.probe_ref_len)},
+                           {pr->probe_alt_off, 4 * n_probes, reinterpret_cast<const void**>(&pd.in.probe_alt_off)},
+                           {pr->probe_alt_len, 4 * n_probes, reinterpret_cast<const void**>(&pd.in.probe_alt_len)},
+                           {pr->alt_pool, pool_bytes, reinterpret_cast<const void**>(&pd.in.alt_pool)}};
+    for (int i = 0; i < 6; ++i) {
+      MA_HIP(ctx, ctx->pb_in[i].reserve(items[i].bytes + 16));
+      if (items[i].bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->pb_in[i].p, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+      *items[i].dst = ctx->pb_in[i].p;
+    }
+  } else {
+    pd.in = *pr;
+  }
+  DBatch d;
+  MA_TRY(stage_batch(ctx, b, &d));
+  OutMirror<ma_asm_out_t> a;
+  MA_TRY(a.prepare(ctx, out, asm_fields(ctx->prm, d.n_windows), 2, false));
+  OutMirror<ma_probe_out_t> pm;
+  MA_TRY(pm.prepare(ctx, po, probe_fields(ctx->prm, n_probes), 96, false));
+  pd.o = pm.dev;
+  MA_HIP(ctx, ctx->pb_err.reserve(sizeof(u32)));
+  MA_HIP(ctx, hipMemsetAsync(ctx->pb_err.p, 0, sizeof(u32), ctx->stream));
+  pd.err = ctx->pb_err.as<u32>();
+  // the call runs as an exporting one -- the clean kernels that leave marks, the rung-by-rung ladder -- without the export's
+  // arrays: with ctx->probe set the export's launches are the probe kernels' (graph_export.hip)
+  MA_HIP(ctx, ctx->gx_mark.reserve(sizeof(u32) * kGxMark * (static_cast<size_t>(d.n_windows) + 1)));
+  MA_HIP(ctx, ctx->gx_routes.reserve(4 * sizeof(unsigned long long)));
+  MA_HIP(ctx, hipMemsetAsync(ctx->gx_routes.p, 0, 4 * sizeof(unsigned long long), ctx->stream));  // (nothing is exported)
+  GxDev dev{};
+  dev.mark = ctx->gx_mark.as<u32>();
+  dev.routes = ctx->gx_routes.as<unsigned long long>();
+  MA_HIP(ctx, ctx->ws_misc.reserve(8ull * (d.n_windows + 1)));
+  u32* approx = ctx->ws_misc.as<u32>();
+  u32* exact = approx + d.n_windows;
+  MA_TRY(launch_gate(ctx, d, approx, exact));
+  ctx->gx = &dev;
+  ctx->probe = &pd;
+  int rc = launch_assemble(ctx, d, a.dev, approx);
+  ctx->gx = nullptr;
+  ctx->probe = nullptr;
+  MA_TRY(rc);
+  MA_TRY(run_probe_reads(ctx, d, a.dev, pd));
+  u32 err = 0;
+  MA_HIP(ctx, hipMemcpyAsync(&err, pd.err, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  MA_HIP(ctx, ma_stream_sync(ctx));  // (`err` is this frame's: the copy has landed before anything below can return)
+  MA_TRY(a.download(ctx));
+  MA_TRY(pm.download(ctx));
+  if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
+  if (err & 1u) return MA_ERR_ARG;
+  if (err & 2u) return MA_ERR_PARAM;
   return MA_OK;
 }
 

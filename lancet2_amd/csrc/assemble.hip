@@ -633,6 +633,9 @@ int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& out, const
             MA_TRY_RC(ma_dev_stats(ctx, &acc));
             hipLaunchKernelGGL(k_workload_stats, dim3(ws.n_active), dim3(256), 0, ctx->stream, ws, acc);
           }
+          // a probe call (ma_assemble_probe_batch): the raw graph as the clean pass receives it -- the survivors of the first
+          // low-coverage pass -- against the window's probes, before the clean kernels merge and prune it
+          if (ctx->probe) MA_TRY_RC(run_probe_raw(ctx, b, ws, *ctx->probe));
           MA_TRY_RC(run_clean_pass(ctx, b, ws, out));
         }
       }

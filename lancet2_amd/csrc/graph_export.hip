@@ -18,10 +18,6 @@ namespace ma {
 
 namespace {
 
-__device__ __forceinline__ u32 gx_sd_st(u32 d) { return d & 0x7FFFu; }
-__device__ __forceinline__ u32 gx_sd_ln(u32 d) { return (d >> 15) & 0x7FFFu; }
-__device__ __forceinline__ u32 gx_sd_rc(u32 d) { return (d >> 30) & 1u; }
-
 __global__ void k_graph_export_clear(ma_graph_out_t o, const u32* win_status, int n, int only_overflowed) {
   int const i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -50,30 +46,13 @@ __global__ __launch_bounds__(64) void k_graph_export(DBatch b, GraphWs ws, GxDev
   }
   __syncthreads();
 
-  // the arrays the reporting route left: the raw graph of k_clean, or the compact graph of the tail kernels
-  bool const raw = route == kGxRouteClean;
-  size_t const nb = static_cast<size_t>(a) * (raw ? ws.nc : ws.vc);
-  u32 const n = raw ? ws.n_nodes[a] : ws.cg_hdr[static_cast<size_t>(a) * kCgHdr];
-  u32 const ecap = raw ? static_cast<u32>(kEdgeCap) : static_cast<u32>(kCgEdgeCap);
-  const u32* cnt = (raw ? ws.nd_cnt : ws.cg_cnt) + nb * S;
-  const u32* comp = (raw ? ws.nd_comp : ws.cg_comp) + nb;
-  const u32* len = (raw ? ws.nd_len : ws.cg_len) + nb;
-  const u32* edge = (raw ? ws.nd_edge : ws.cg_edge) + nb * ecap;
-  const u8* nedge = (raw ? ws.nd_nedge : ws.cg_nedge) + nb;
-  const u8* alive = (raw ? ws.nd_alive : ws.cg_alive) + nb;
-  const u8* label = (raw ? ws.nd_label : ws.cg_label) + nb;
-  const u8* sign = (raw ? ws.nd_sign : ws.cg_sign) + nb;
-  const u32* head = (raw ? ws.nd_head : ws.cg_head) + nb;
-  const u32* snext = (raw ? ws.sl_next : ws.cg_snext) + nb;
-  const u32* sdesc = (raw ? ws.sl_desc : ws.cg_sdesc) + nb;
-  const u32* bsrc = (raw ? ws.nd_src : ws.cg_bsrc) + nb;
-  const u32* blen = raw ? nullptr : ws.cg_blen + nb;  // (raw graph: every base string is an original k-mer)
-  const u8* bsign = (raw ? ws.nd_sign : ws.cg_bsign) + nb;
-  const u8* pool = raw ? nullptr : ws.cg_pool + static_cast<size_t>(a) * ws.pool_cap;
-  const u8* refb = b.ref_bases + b.ref_off[w];
-  const u8* readb = b.read_bases + b.read_off[b.read_win_off[w]];
-  // work lists in the route's scratch (32 words per node of capacity; the clean kernels are done with it): 3 n words
-  u32* const scratch = raw ? ws.scratch + nb * 32 : ws.cg_scratch + static_cast<size_t>(a) * ws.cg_sc * 32;
+  // the arrays the reporting route left: the raw graph of k_clean, or the compact graph of the tail kernels (graph_ws.h)
+  GxNodes const g = gx_nodes(b, ws, a, w, route);
+  u32 const n = g.n, ecap = g.ecap;
+  const u32 *cnt = g.cnt, *comp = g.comp, *len = g.len, *edge = g.edge;
+  const u8 *nedge = g.nedge, *alive = g.alive, *label = g.label, *sign = g.sign;
+  // work lists in the route's scratch: 3 n words
+  u32* const scratch = g.scratch;
   u32* const slot_of = scratch;       // [n] node -> slot of the window's export, kNoNode: not exported
   u32* const seq_at = scratch + n;    // [n] where its bases start in the window's pool
   u32* const edge_at = scratch + 2 * static_cast<size_t>(n);  // [n] where its edges start
@@ -165,23 +144,8 @@ __global__ __launch_bounds__(64) void k_graph_export(DBatch b, GraphWs ws, GxDev
       gx.o.edge_kind[e0 + ea] = static_cast<u8>(e & 3u);
       ++ea;
     }
-    // the node's sequence as stored: its slices head to tail, each one `ln` bases of a base string from `st` on -- read
-    // backwards and complemented once for a reverse-complemented slice and once more for a base string kept on the
-    // other strand
-    u32 pos = 0, steps = 0;
-    for (u32 s = head[i]; s != kNoNode && s < n && pos < ln && steps < n; s = snext[s], ++steps) {
-      u32 const d = sdesc[s], st = gx_sd_st(d), sl = gx_sd_ln(d);
-      u32 const bl = blen ? blen[s] : K, sv = bsrc[s];
-      const u8* p = (sv & 0x80000000u) ? readb + (sv & 0x3FFFFFFFu) : ((pool && (sv & 0x40000000u)) ? pool + (sv & 0x3FFFFFFFu) : refb + sv);
-      bool const flip = (gx_sd_rc(d) != 0u) != (bsign[s] == 0);  // an odd number of turns: backwards and complemented
-      for (u32 j = 0; j < sl && pos < ln; ++j) {
-        u32 pp = st + j;
-        if (gx_sd_rc(d)) pp = bl - 1u - pp;
-        if (!bsign[s]) pp = bl - 1u - pp;
-        u8 const ch = pp < bl ? p[pp] : static_cast<u8>('N');
-        seq[at + pos++] = flip ? dev_complement(ch) : ch;
-      }
-    }
+    // the node's sequence as stored (graph_ws.h: gx_spell_node)
+    u32 pos = gx_spell_node(g, i, ln, K, [seq, at](u32 at_pos, u8 ch) { seq[at + at_pos] = ch; });
     for (; pos < ln; ++pos) seq[at + pos] = 'N';  // (a list shorter than the node's length: never seen; defined bytes all the same)
   }
 }
@@ -190,6 +154,7 @@ __global__ __launch_bounds__(64) void k_graph_export(DBatch b, GraphWs ws, GxDev
 
 int run_graph_export_clear(ma_ctx* ctx, const GxDev& gx, const u32* win_status, int n, bool only_overflowed) {
   if (n == 0) return MA_OK;
+  if (ctx->probe) return run_probe_clear(ctx, *ctx->probe, win_status, n, only_overflowed);  // (a probe call: gx.o has no arrays)
   hipLaunchKernelGGL(k_graph_export_clear, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, gx.o, win_status, n, only_overflowed ? 1 : 0);
   MA_HIP(ctx, hipGetLastError());
   return MA_OK;
@@ -197,6 +162,7 @@ int run_graph_export_clear(ma_ctx* ctx, const GxDev& gx, const u32* win_status, 
 
 int run_graph_export(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const GxDev& gx) {
   if (ws.n_active == 0) return MA_OK;
+  if (ctx->probe) return run_probe_nodes(ctx, b, ws, gx.mark, *ctx->probe);  // the probes' rows instead of the graph's
   ctx->tic("k_graph_export");
   hipLaunchKernelGGL(k_graph_export, dim3(ws.n_active), dim3(64), 0, ctx->stream, b, ws, gx);
   ctx->toc();

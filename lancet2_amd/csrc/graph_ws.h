@@ -152,6 +152,21 @@ struct GxDev {
 int run_graph_export(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const GxDev& gx);  // graph_export.hip
 int run_graph_export_clear(ma_ctx* ctx, const GxDev& gx, const u32* win_status, int n, bool only_overflowed);
 
+// ---- probe variants (ma_assemble_probe_batch: probe.hip) ----
+// The call runs as an exporting call (ctx->gx set, with no arrays in GxDev::o: the marking clean kernels, the rung-by-rung
+// ladder) and ctx->probe says where the probes lie and where their rows go; run_graph_export / run_graph_export_clear hand
+// over to the probe kernels then.
+struct ProbeDev {
+  ma_probes_t in;      // device pointers
+  ma_probe_out_t o;    // the caller's arrays (device pointers), addressed by probe
+  u32* err;            // [1] bit 0: a probe outside its window (MA_ERR_ARG), bit 1: a limit exceeded (MA_ERR_PARAM)
+  u32 max_comps;
+};
+int run_probe_clear(ma_ctx* ctx, const ProbeDev& pd, const u32* win_status, int n, bool only_overflowed);
+int run_probe_raw(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const ProbeDev& pd);                    // after run_build_pass
+int run_probe_nodes(ma_ctx* ctx, const DBatch& b, const GraphWs& ws, const u32* mark, const ProbeDev& pd); // after the clean kernels
+int run_probe_reads(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& a, const ProbeDev& pd);              // end of the call
+
 // the k window w is built / cleaned with in the current pass
 __device__ __forceinline__ int win_kmer(GraphWs const& ws, int w) {
   u32 const k = ws.win_k[w];
@@ -175,6 +190,70 @@ __device__ __forceinline__ u64 dev_fmix64(u64 x) {
   x *= 0xc4ceb9fe1a85ec53ULL;
   x ^= x >> 33;
   return x;
+}
+
+// ---- the node arrays a reporting clean route left behind, as k_graph_export and k_probe_nodes read them ----
+__device__ __forceinline__ u32 gx_sd_st(u32 d) { return d & 0x7FFFu; }
+__device__ __forceinline__ u32 gx_sd_ln(u32 d) { return (d >> 15) & 0x7FFFu; }
+__device__ __forceinline__ u32 gx_sd_rc(u32 d) { return (d >> 30) & 1u; }
+
+struct GxNodes {
+  u32 n, ecap;
+  const u32 *cnt, *comp, *len, *edge;
+  const u8 *nedge, *alive, *label, *sign;
+  const u32 *head, *snext, *sdesc, *bsrc, *blen;  // blen null: every base string is an original k-mer (raw graph)
+  const u8 *bsign, *pool;                         // pool null: raw graph
+  const u8 *refb, *readb;
+  u32* scratch;  // the route's scratch (32 words per node of capacity; the clean kernels are done with it)
+};
+// slot a (window w) as `route` reported it: the raw graph of k_clean, or the compact graph of the tail kernels
+__device__ __forceinline__ GxNodes gx_nodes(DBatch const& b, GraphWs const& ws, int a, int w, u32 route) {
+  bool const raw = route == kGxRouteClean;
+  size_t const nb = static_cast<size_t>(a) * (raw ? ws.nc : ws.vc);
+  u32 const S = static_cast<u32>(ws.num_samples);
+  GxNodes g;
+  g.n = raw ? ws.n_nodes[a] : ws.cg_hdr[static_cast<size_t>(a) * kCgHdr];
+  g.ecap = raw ? static_cast<u32>(kEdgeCap) : static_cast<u32>(kCgEdgeCap);
+  g.cnt = (raw ? ws.nd_cnt : ws.cg_cnt) + nb * S;
+  g.comp = (raw ? ws.nd_comp : ws.cg_comp) + nb;
+  g.len = (raw ? ws.nd_len : ws.cg_len) + nb;
+  g.edge = (raw ? ws.nd_edge : ws.cg_edge) + nb * g.ecap;
+  g.nedge = (raw ? ws.nd_nedge : ws.cg_nedge) + nb;
+  g.alive = (raw ? ws.nd_alive : ws.cg_alive) + nb;
+  g.label = (raw ? ws.nd_label : ws.cg_label) + nb;
+  g.sign = (raw ? ws.nd_sign : ws.cg_sign) + nb;
+  g.head = (raw ? ws.nd_head : ws.cg_head) + nb;
+  g.snext = (raw ? ws.sl_next : ws.cg_snext) + nb;
+  g.sdesc = (raw ? ws.sl_desc : ws.cg_sdesc) + nb;
+  g.bsrc = (raw ? ws.nd_src : ws.cg_bsrc) + nb;
+  g.blen = raw ? nullptr : ws.cg_blen + nb;
+  g.bsign = (raw ? ws.nd_sign : ws.cg_bsign) + nb;
+  g.pool = raw ? nullptr : ws.cg_pool + static_cast<size_t>(a) * ws.pool_cap;
+  g.refb = b.ref_bases + b.ref_off[w];
+  g.readb = b.read_bases + b.read_off[b.read_win_off[w]];
+  g.scratch = raw ? ws.scratch + nb * 32 : ws.cg_scratch + static_cast<size_t>(a) * ws.cg_sc * 32;
+  return g;
+}
+// Node i's sequence as stored, base by base to put(position, letter): its slices head to tail, each one `ln` bases of a base
+// string from `st` on -- read backwards and complemented once for a reverse-complemented slice and once more for a base
+// string kept on the other strand.  Returns how many of the node's `ln` bases the slice list spelled.
+template <class Put>
+__device__ __forceinline__ u32 gx_spell_node(GxNodes const& g, u32 i, u32 ln, u32 K, Put&& put) {
+  u32 pos = 0, steps = 0;
+  for (u32 s = g.head[i]; s != kNoNode && s < g.n && pos < ln && steps < g.n; s = g.snext[s], ++steps) {
+    u32 const d = g.sdesc[s], st = gx_sd_st(d), sl = gx_sd_ln(d);
+    u32 const bl = g.blen ? g.blen[s] : K, sv = g.bsrc[s];
+    const u8* p = (sv & 0x80000000u) ? g.readb + (sv & 0x3FFFFFFFu) : ((g.pool && (sv & 0x40000000u)) ? g.pool + (sv & 0x3FFFFFFFu) : g.refb + sv);
+    bool const flip = (gx_sd_rc(d) != 0u) != (g.bsign[s] == 0);  // an odd number of turns: backwards and complemented
+    for (u32 j = 0; j < sl && pos < ln; ++j) {
+      u32 pp = st + j;
+      if (gx_sd_rc(d)) pp = bl - 1u - pp;
+      if (!g.bsign[s]) pp = bl - 1u - pp;
+      u8 const ch = pp < bl ? p[pp] : static_cast<u8>('N');
+      put(pos++, flip ? dev_complement(ch) : ch);
+    }
+  }
+  return pos;
 }
 
 }  // namespace ma

@@ -63,6 +63,7 @@ struct KernelTimer {
 };
 
 struct GxDev;  // graph_ws.h: where a call that exports the graphs (ma_assemble_graph_batch) writes
+struct ProbeDev;  // graph_ws.h: the probes of ma_assemble_probe_batch and where their rows go
 // where a call that exports the POA graphs (ma_msa_graph_batch) writes: the caller's arrays (device pointers), addressed by
 // GLOBAL window id, and the four pass counters of ma_last_poa_export
 struct PoaExp {
@@ -136,6 +137,11 @@ struct ma_ctx {
   // counters of ma_last_graph_export (device, read when asked for)
   const ma::GxDev* gx = nullptr;
   ma::DevBuf gx_mark, gx_routes;
+  // ma_assemble_probe_batch: non-null (beside gx) while its assembly runs -- assemble.hip launches k_probe_raw between the
+  // build and the clean pass, graph_export.hip hands the export's two launches over to probe.hip; the staged probe arrays of
+  // a MA_MEM_HOST call and the call's error word
+  const ma::ProbeDev* probe = nullptr;
+  ma::DevBuf pb_in[6], pb_err;
   // ma_msa_graph_batch: non-null while its POA stage runs (poa.hip: launch_msa takes the exporting kernels, host-counted
   // rounds); the device counters of that call and the counts ma_last_poa_export reports
   const ma::PoaExp* px = nullptr;

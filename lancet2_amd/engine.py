@@ -55,6 +55,8 @@ def load_library(path=None):
     if hasattr(lib, "ma_assemble_graph_batch"):  # (likewise: a build of before the graph export)
         lib.ma_assemble_graph_batch.argtypes = [C.c_void_p] * 4
         lib.ma_last_graph_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+    if hasattr(lib, "ma_assemble_probe_batch"):  # (likewise: a build of before the probe call)
+        lib.ma_assemble_probe_batch.argtypes = [C.c_void_p] * 5
     if hasattr(lib, "ma_msa_graph_batch"):  # (likewise: a build of before the POA export)
         lib.ma_msa_graph_batch.argtypes = [C.c_void_p] * 5
         lib.ma_last_poa_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
@@ -172,6 +174,32 @@ class Engine:
         if n < 0:
             raise EngineError(f"ma_last_graph_export failed ({n}): {self.lib.ma_last_error(self.h).decode()}")
         return {k: int(buf[i]) for i, k in enumerate(capi.GRAPH_EXPORT_KEYS) if i < n}
+
+    def assemble_probes(self, arrs, n, nr, probes):
+        """ma_assemble_probe_batch: assemble() + one row per probe (include/microasm.h: ma_probe_out_t).  `probes`: the dict
+        of capi.pack_probes -- probe_win_off[n + 1], then pos, ref_len, alt_off, alt_len per probe and the ALT pool.  Returns
+        (asm, probe_out); raises EngineError with .rc = the ma_error."""
+        pr = {k: np.ascontiguousarray(probes[k], dtype=dt) for k, dt in capi.PROBE_DTYPES.items()}
+        n_probes = int(pr["probe_win_off"][n])
+        out = self._alloc(capi.asm_out_spec(self.p, n))
+        spec = capi.probe_out_spec(self.p, n_probes)
+        po = self._alloc(spec)
+        # (an empty array has no address worth passing: every member is required to be non-NULL)
+        held = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in list(pr.items()) + list(po.items())}
+        b = capi.make_batch_struct(arrs, n, nr)
+        self.assemble_probes_device(b, capi.fill_struct(capi.AsmOut, out), capi.fill_struct(capi.Probes, held),
+                                    capi.fill_struct(capi.ProbeOut, held))
+        return out, po
+
+    def assemble_probes_device(self, batch_struct, asm, probes, probe_out):
+        """ma_assemble_probe_batch on caller-made structs (either memory space); probes / probe_out None: a null pointer,
+        the plain call"""
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        rc = self.lib.ma_assemble_probe_batch(self.h, C.byref(batch_struct), C.byref(asm), ref(probes), ref(probe_out))
+        if rc != 0:
+            e = EngineError(f"ma_assemble_probe_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
 
     def msa(self, arrs, n, nr, asm):
         out = self._alloc(capi.var_out_spec(self.p, n))

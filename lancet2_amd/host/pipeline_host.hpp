@@ -1888,4 +1888,125 @@ inline std::string RenderComponentFasta(const ma_params_t& p, const ma_asm_out_t
   return out;
 }
 
+// ---- probe variants: the reference's --probe-variants input and --probe-results output around ma_assemble_probe_batch ----
+struct ProbeVariant {  // cbdg/probe_index.h:18-35
+  std::string chrom, ref, alt;
+  uint64_t start0 = 0;
+  uint32_t raw_alt = 0;
+};
+// missed_variants.txt (cbdg/probe_index.cpp:144-204): a header line, then tab-separated chrom, 0-based start, end, ref, alt,
+// type, length, classification, raw_alt_count, ...; like the reference a line of fewer than nine fields, or whose start or
+// raw_alt_count is no number, is skipped, and a probe's id is its index among the lines that were taken
+inline std::vector<ProbeVariant> LoadProbeVariants(std::string const& path) {
+  std::ifstream in(path);
+  if (!in) throw std::runtime_error("--probe-variants: cannot open " + path);
+  std::vector<ProbeVariant> out;
+  std::string line;
+  std::getline(in, line);  // header
+  while (std::getline(in, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    std::vector<std::string> f;
+    for (size_t at = 0;;) {
+      size_t const tab = line.find('\t', at);
+      f.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+      if (tab == std::string::npos) break;
+      at = tab + 1;
+    }
+    auto number = [](std::string const& s, uint64_t* v) {
+      if (s.empty() || s.find_first_not_of("0123456789") != std::string::npos || s.size() > 18) return false;
+      *v = std::stoull(s);
+      return true;
+    };
+    uint64_t start = 0, raw = 0;
+    if (f.size() < 9 || !number(f[8], &raw) || raw > 65535 || !number(f[1], &start)) continue;
+    ProbeVariant v;
+    v.chrom = f[0]; v.ref = f[3]; v.alt = f[4];
+    v.start0 = start; v.raw_alt = static_cast<uint32_t>(raw);
+    out.push_back(std::move(v));
+  }
+  return out;
+}
+
+// the header of probe_results.tsv (cbdg/probe_results_writer.cpp:51-59), forty columns
+inline constexpr const char* kProbeResultsHeader =
+    "probe_id\tchrom\tpos\tref\talt\twindow\tn_raw_alt_reads\tkmer_size\tn_expected_alt_kmers\tn_alt_kmers_in_reads\t"
+    "comp_id\tn_comp_nodes\tn_split_across_comps\tn_surviving_build\tn_surviving_lowcov1\tn_surviving_compress1\t"
+    "n_surviving_lowcov2\tn_surviving_compress2\tn_surviving_tips\thap_indices\tis_traversal_limited\t"
+    "is_graph_cycle\tis_graph_complex\tis_no_anchor\tis_short_anchor\tis_variant_in_anchor\t"
+    "n_last_edge_kmers\tn_last_interior_kmers\tn_last_chain_gaps\t"
+    "msa_shift_bp\tis_msa_exact_match\tis_msa_shifted\tis_msa_subsumed\t"
+    "n_geno_true_alt_reads\tn_geno_total_ref_reads\tn_geno_reassigned_to_ref\t"
+    "n_geno_reassigned_to_wrong_alt\tn_geno_non_overlapping\tis_geno_has_alt_support\tis_geno_no_overlap\n";
+
+// The probes of one batch as ma_probes_t wants them.  A variant is activated in every window whose region holds its start
+// (probe_tracker.cpp:259-266: same chromosome, region start <= start < region end) -- unless its REF allele runs past the
+// window's end, an allele is longer than 256 bases or the window already has 256 probes (the call's limits): those are counted
+// in `skipped`.  id[i] = the variant of probe i.
+struct ProbeBatch {
+  std::vector<uint32_t> win_off, pos, ref_len, alt_off, alt_len, id;
+  std::vector<uint8_t> pool;
+  size_t skipped = 0;
+  ma_probes_t View() const {
+    ma_probes_t v{};
+    v.probe_win_off = win_off.data(); v.probe_pos = pos.data(); v.probe_ref_len = ref_len.data();
+    v.probe_alt_off = alt_off.data(); v.probe_alt_len = alt_len.data(); v.alt_pool = pool.data();
+    return v;
+  }
+};
+template <class Windows, class ChromName>
+inline ProbeBatch ActivateProbes(std::vector<ProbeVariant> const& variants, Windows const& windows, ChromName&& chrom_name) {
+  ProbeBatch pb;
+  pb.win_off.push_back(0);
+  for (auto const& w : windows) {
+    uint64_t const s0 = w.start1 - 1, e0 = w.end1;  // the window's bases, 0-based half-open
+    std::string const& name = chrom_name(w.chrom);
+    uint32_t taken = 0;
+    for (size_t i = 0; i < variants.size(); ++i) {
+      ProbeVariant const& v = variants[i];
+      if (v.chrom != name || v.start0 < s0 || v.start0 >= e0) continue;
+      if (v.start0 + v.ref.size() > e0 || v.ref.size() > 256 || v.alt.size() > 256 || taken == 256) {
+        ++pb.skipped;
+        continue;
+      }
+      pb.pos.push_back(static_cast<uint32_t>(v.start0 - s0));
+      pb.ref_len.push_back(static_cast<uint32_t>(v.ref.size()));
+      pb.alt_off.push_back(static_cast<uint32_t>(pb.pool.size()));
+      pb.alt_len.push_back(static_cast<uint32_t>(v.alt.size()));
+      pb.pool.insert(pb.pool.end(), v.alt.begin(), v.alt.end());
+      pb.id.push_back(static_cast<uint32_t>(i));
+      ++taken;
+    }
+    pb.win_off.push_back(static_cast<uint32_t>(pb.pos.size()));
+  }
+  pb.pool.push_back(0);  // (never empty: the call wants a pointer)
+  for (auto* v : {&pb.pos, &pb.ref_len, &pb.alt_off, &pb.alt_len})
+    if (v->empty()) v->push_back(0);
+  return pb;
+}
+
+// The lines of probe i (window w of the batch, named `region`): one per row of comp_* -- one with comp_id "." for a window
+// without a component, so that the reads' and the raw graph's counts are not lost.  Columns the engine does not produce are
+// ".": n_comp_nodes, n_split_across_comps, build, compress1 / 2, lowcov2, the structural flags, the MSA and genotyper columns.
+inline std::string RenderProbeLines(const ma_params_t& p, const ma_asm_out_t& a, const ma_probe_out_t& o, size_t i, int w, uint32_t probe_id,
+                                    ProbeVariant const& v, std::string const& region) {
+  size_t const MC = static_cast<size_t>(p.max_comps);
+  uint32_t const ncomp = a.win_ncomp[w];
+  std::string const head = std::to_string(probe_id) + "\t" + v.chrom + "\t" + std::to_string(v.start0) + "\t" + v.ref + "\t" + v.alt + "\t" + region +
+                           "\t" + std::to_string(v.raw_alt) + "\t" + std::to_string(o.pb_k[i]) + "\t" + std::to_string(o.pb_alt_kmers[i]) + "\t" +
+                           std::to_string(o.pb_in_reads[2 * i]) + "\t";
+  std::string out;
+  for (uint32_t c = 0; c < (ncomp ? ncomp : 1u); ++c) {
+    const uint32_t* fin = o.pb_final + 4 * (i * MC + c);
+    std::string haps;
+    if (ncomp)
+      for (uint32_t h = 0; h < 32; ++h)
+        if (o.pb_hap_mask[i * MC + c] >> h & 1u) haps += (haps.empty() ? "" : ",") + std::to_string(h);
+    auto fin_or_dot = [&](int x) { return ncomp ? std::to_string(fin[x]) : std::string("."); };
+    out += head + (ncomp ? std::to_string(c) : std::string(".")) + "\t.\t.\t.\t" + std::to_string(o.pb_lowcov1[4 * i]) + "\t.\t.\t.\t" + fin_or_dot(0) +
+           "\t" + (haps.empty() ? "." : haps) + "\t.\t.\t.\t.\t.\t.\t" + fin_or_dot(1) + "\t" + fin_or_dot(2) + "\t" + fin_or_dot(3) +
+           "\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\n";
+  }
+  return out;
+}
+
 }  // namespace lancet2_amd::host
