@@ -157,19 +157,37 @@ void DumpBatch(const std::string& dir, FlatBatch const& fb) {
   };
   put("ref_bases.u8", fb.ref_bases.data(), fb.ref_bases.size());
   put("ref_off.u32", fb.ref_off.data(), 4 * fb.ref_off.size());
-  put("read_win_off.u32", fb.read_win_off.data(), 4 * fb.read_win_off.size());
-  put("read_off.u64", fb.read_off.data(), 8 * fb.read_off.size());
-  put("read_bases.u8", fb.read_bases.data(), fb.read_bases.size());
-  put("read_quals.u8", fb.read_quals.data(), fb.read_quals.size());
-  if (fb.packed_mode) put("bases4.u8", fb.bases4.data(), fb.bases4.size());  // (--packed-reads: read_bases.u8 is the pad alone)
-  put("read_qname_id.u32", fb.read_qname_id.data(), 4 * fb.read_qname_id.size());
-  put("read_sample.u8", fb.read_sample.data(), fb.read_sample.size());
-  put("read_flags.u8", fb.read_flags.data(), fb.read_flags.size());
-  put("read_hint.i32", fb.read_hint.data(), 4 * fb.read_hint.size());
-  put("read_mapq.u8", fb.read_mapq.data(), fb.read_mapq.size());  // the read metadata of ma_read_meta_t
-  put("read_mflags.u8", fb.read_mflags.data(), fb.read_mflags.size());
-  put("read_isize.i32", fb.read_isize.data(), 4 * fb.read_isize.size());
-  put("read_start.i32", fb.read_start.data(), 4 * fb.read_start.size());
+  if (fb.raw_mode) {  // --raw-records: the arrays of ma_records_t (include/microasm.h) beside the window list; no read arrays yet
+    ma_records_t const& r = fb.records;
+    size_t const n = static_cast<size_t>(r.n_records), nw = static_cast<size_t>(r.n_windows), ns = static_cast<size_t>(r.n_samples_in);
+    int32_t const counts[2] = {r.n_samples_in, r.n_refs};
+    put("blob.u8", r.blob, static_cast<size_t>(r.blob_bytes));
+    put("rec_off.u64", r.rec_off, 8 * n);
+    put("rec_len.u32", r.rec_len, 4 * n);
+    put("rec_win_off.u32", r.rec_win_off, 4 * (nw + 1));
+    put("rec_sample.u8", r.rec_sample, n);
+    put("sample_index.u8", r.sample_index, ns);
+    put("sample_case.u8", r.sample_case, ns);
+    put("sample_rank.u32", r.sample_rank, 4 * ns);
+    put("ref_map.i32", r.ref_map, 4 * ns * static_cast<size_t>(r.n_refs));
+    put("counts.i32", counts, sizeof counts);  // n_samples_in, n_refs
+    put("win_chrom.i32", r.win_chrom, 4 * nw);
+    put("win_start0.i64", r.win_start0, 8 * nw);
+  } else {
+    put("read_win_off.u32", fb.read_win_off.data(), 4 * fb.read_win_off.size());
+    put("read_off.u64", fb.read_off.data(), 8 * fb.read_off.size());
+    put("read_bases.u8", fb.read_bases.data(), fb.read_bases.size());
+    put("read_quals.u8", fb.read_quals.data(), fb.read_quals.size());
+    if (fb.packed_mode) put("bases4.u8", fb.bases4.data(), fb.bases4.size());  // (--packed-reads: read_bases.u8 is the pad alone)
+    put("read_qname_id.u32", fb.read_qname_id.data(), 4 * fb.read_qname_id.size());
+    put("read_sample.u8", fb.read_sample.data(), fb.read_sample.size());
+    put("read_flags.u8", fb.read_flags.data(), fb.read_flags.size());
+    put("read_hint.i32", fb.read_hint.data(), 4 * fb.read_hint.size());
+    put("read_mapq.u8", fb.read_mapq.data(), fb.read_mapq.size());  // the read metadata of ma_read_meta_t
+    put("read_mflags.u8", fb.read_mflags.data(), fb.read_mflags.size());
+    put("read_isize.i32", fb.read_isize.data(), 4 * fb.read_isize.size());
+    put("read_start.i32", fb.read_start.data(), 4 * fb.read_start.size());
+  }
   std::vector<uint64_t> wins;
   for (auto const& w : fb.windows) {
     wins.push_back(static_cast<uint64_t>(w.chrom));
@@ -347,7 +365,7 @@ long WriteProbeResults(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& r
   return written;
 }
 
-AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed) {
+AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed, bool keep_raw) {
   bool const bam = path.size() > 4 && path.substr(path.size() - 4) == ".bam";
 #ifdef LANCET2_AMD_WITH_ZLIB
   if (bam) {
@@ -355,9 +373,9 @@ AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bo
     // without one the whole file is read once
     for (std::string const& bai : {path + ".bai", path.substr(0, path.size() - 4) + ".bai"}) {
       std::ifstream probe(bai, std::ios::binary);
-      if (probe && !getenv("PIPELINE_NO_INDEX")) return AlignmentSource::OpenIndexedBam(path, bai, ref, keep_packed);
+      if (probe && !getenv("PIPELINE_NO_INDEX")) return AlignmentSource::OpenIndexedBam(path, bai, ref, keep_packed, keep_raw);
     }
-    return AlignmentSource::LoadBam(path, ref, keep_packed);
+    return AlignmentSource::LoadBam(path, ref, keep_packed, keep_raw);
   }
 #else
   if (bam) throw std::runtime_error("built without zlib (-DLANCET2_AMD_WITH_ZLIB -lz): BAM input is not available");
@@ -385,7 +403,7 @@ int main(int argc, char** argv) {
   ReadCollector::Params rp;
   ma_params_t prm;
   ma_default_params(&prm);
-  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false, poa_retry = false;
+  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false, poa_retry = false, raw_records = false;
   int batch_windows = 512;
   int extract_threads = static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
   for (int i = 1; i < argc; ++i) {
@@ -419,6 +437,7 @@ int main(int argc, char** argv) {
     else if (a == "--probe-results") probe_results_path = next();    // ... and where their records go
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
+    else if (a == "--raw-records") raw_records = true;  // BAM records as they are to the engine: ma_flatten_records_batch, then the chained call
     else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
     else if (a == "--poa-retry") poa_retry = true;  // ma_set_poa_retry: a second POA pass over the windows whose graph overflowed
     else if (a == "--extract-only") extract_only = true;  // stage 1 alone (with --dump): no device needed
@@ -446,11 +465,28 @@ int main(int argc, char** argv) {
                          "                  per (probe, window, component) -- one with comp_id . for a window without a component: kmer_size,\n"
                          "                  n_expected_alt_kmers, n_alt_kmers_in_reads, n_surviving_lowcov1, n_surviving_tips, hap_indices and the\n"
                          "                  three n_last_* columns; every other result column is \".\".  Not with --packed-reads\n"
+                         "  --raw-records   BAM inputs only: the kept records go to the engine as the file has them; ma_flatten_records_batch\n"
+                         "                  sorts them, interns the names and lays out the bases, then the chained call runs as with\n"
+                         "                  --packed-reads --read-meta.  With --extract-only --dump: the ma_records_t arrays\n"
                          "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
                          "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
                          "                  all 24 FORMAT values.  Without it those six are \".\"\n"
                          "  --poa-retry     windows whose POA graph ran out of nodes or of per-node edge slots (MA_W_VAR_OVERFLOW that larger\n"
                          "                  caps do not cure) are re-run by the engine with a larger graph.  Default: off\n");
+    return 2;
+  }
+  if (raw_records && (collect_reads || rp.extract_pairs || packed_reads)) {
+    std::fprintf(stderr, "pipeline_driver: --raw-records is a collector of its own (not with --collect-reads / --extract-pairs / --packed-reads)\n");
+    return 2;
+  }
+  for (auto const* paths : {&normals, &tumors})
+    for (std::string const& path : *paths)
+      if (raw_records && !(path.size() > 4 && path.substr(path.size() - 4) == ".bam")) {
+        std::fprintf(stderr, "pipeline_driver: --raw-records hands BAM records to the engine; %s is not a BAM file\n", path.c_str());
+        return 2;
+      }
+  if (raw_records && (!graphs_dir.empty() || !probe_variants_path.empty() || !msa_dir.empty())) {  // (stage calls on ASCII reads)
+    std::fprintf(stderr, "pipeline_driver: --out-graphs-dir / --probe-variants / --out-msa-dir need ASCII reads (not with --raw-records)\n");
     return 2;
   }
   if (packed_reads && (collect_reads || rp.extract_pairs)) {
@@ -474,12 +510,13 @@ int main(int argc, char** argv) {
     return 2;
   }
   rp.packed_reads = packed_reads;
+  rp.raw_records = raw_records;
   Reference const ref = Reference::LoadFasta(ref_path);
   std::vector<AlignmentSource> sources;
   sources.reserve(normals.size() + tumors.size());
   std::vector<SampleInfo> samples;
   auto add_sample = [&](const std::string& path, Tag tag) {
-    sources.push_back(LoadAlignments(path, ref, packed_reads));  // (packed: BAM records keep their sequence bytes)
+    sources.push_back(LoadAlignments(path, ref, packed_reads, raw_records));  // (packed: BAM records keep their sequence bytes)
     std::string name = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
     name = name.substr(0, name.find_last_of('.'));
     samples.push_back({name, tag, nullptr, 0, 0, 0});
@@ -492,6 +529,8 @@ int main(int argc, char** argv) {
     return 5;
   }
   for (size_t i = 0; i < samples.size(); ++i) samples[i].source = &sources[i];
+  FlatBatch::RawTables raw_tables;  // --raw-records: the sample tables and reference maps every batch's ma_records_t points to
+  if (raw_records) raw_tables = MakeRawTables(ReadCollector(rp, samples).Samples());
   prm.num_samples = static_cast<int32_t>(samples.size());
   prm.case_ctrl_mode = (!normals.empty() && !tumors.empty()) ? 1 : 0;  // read_collector.cpp:88-94
   if (wp.window_length + 1 > static_cast<uint32_t>(prm.max_hap_len) - 16) prm.max_hap_len = 3072;  // -w 2500 (cli maximum)
@@ -622,7 +661,7 @@ int main(int argc, char** argv) {
           // the window's reads straight into its flat arrays (ReadCollector::CollectFlat); the reference-shaped path -- a Read
           // per alignment, then FlatBatch::Add -- when the options need it (--extract-pairs) or --collect-reads asks for it
           auto flat = std::make_unique<FlatBatch>();
-          if (!collect_reads && collector.CollectFlat(w, seq, flat.get())) {
+          if (!collect_reads && (raw_records ? collector.CollectRaw(w, seq, flat.get()) : collector.CollectFlat(w, seq, flat.get()))) {
             if (CrossSampleMeanCoverage(collector.Samples(), w.Length()) < static_cast<double>(prm.min_anchor_cov)) sl.st = WindowStatus::SKIPPED_ANCHOR_COVERAGE;
             else sl.flat = std::move(flat);
           } else {
@@ -662,6 +701,7 @@ int main(int argc, char** argv) {
       }
       if (!j.batch) j.batch = std::make_unique<FlatBatch>();
       j.batch->packed_mode = packed_reads;
+      j.batch->raw_mode = raw_records;
       if (hint_reads) j.batch->Reserve(static_cast<size_t>(batch_windows), hint_ref, hint_reads, hint_bases);
       return j;
     };
@@ -686,8 +726,12 @@ int main(int argc, char** argv) {
         auto const ts = Clock::now();
         Job j = std::move(pending.front().job);
         pending.pop_front();
-        j.batch->Seal();
-        if (packed_reads) j.batch->PackReads();
+        if (raw_records) {
+          j.batch->SealRaw(raw_tables);
+        } else {
+          j.batch->Seal();
+          if (packed_reads) j.batch->PackReads();
+        }
         busy_extract += secs(Clock::now() - ts);  // (the Push below may wait for the engine: not this stage's time)
         if (!dump_dir.empty()) {
           char sub[64];
@@ -752,7 +796,9 @@ int main(int argc, char** argv) {
     to_engine.Close();
   });
   // ---- stage 2: engine ----
-  bool const with_meta = read_meta && !vcf_path.empty();
+  // --raw-records: the flattened arrays go to the chained call as --packed-reads --read-meta would bring them
+  bool const with_meta = (read_meta || raw_records) && !vcf_path.empty();
+  bool const engine_packed = packed_reads || raw_records;
   size_t n_graph_files = 0, n_msa_files = 0, n_probe_lines = 0, n_probe_skipped = 0;
   std::vector<ProbeVariant> probe_variants;
   FILE* probe_out = nullptr;
@@ -775,24 +821,28 @@ int main(int argc, char** argv) {
         continue;
       }
       Job* nxt = nullptr;
-      if (to_engine.Peek(&nxt)) {  // uploads under this batch's kernels
-        if (with_meta) ma_prefetch_meta_batch(ctx, packed_reads ? &nxt->batch->packed_view : &nxt->batch->view,
-                                              packed_reads ? &nxt->batch->packed : nullptr, &nxt->batch->meta);
-        else if (packed_reads) ma_prefetch_packed_batch(ctx, &nxt->batch->packed_view, &nxt->batch->packed);
+      if (!raw_records && to_engine.Peek(&nxt)) {  // uploads under this batch's kernels (a raw batch's arrays are made in its own turn)
+        if (with_meta) ma_prefetch_meta_batch(ctx, engine_packed ? &nxt->batch->packed_view : &nxt->batch->view,
+                                              engine_packed ? &nxt->batch->packed : nullptr, &nxt->batch->meta);
+        else if (engine_packed) ma_prefetch_packed_batch(ctx, &nxt->batch->packed_view, &nxt->batch->packed);
         else ma_prefetch_batch(ctx, &nxt->batch->view);
       }
       auto const t0 = Clock::now();
       j.out = std::make_unique<Outputs>();
       j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty(), with_meta);
-      if (!vcf_path.empty())  // one call: the chain with the statistics and INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
-        j.rc = ma_process_cx_batch(ctx, packed_reads ? &j.batch->packed_view : &j.batch->view, packed_reads ? &j.batch->packed : nullptr,
-                                   with_meta ? &j.batch->meta : nullptr, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
-                                   &j.out->fmt, with_meta ? &j.out->fmeta : nullptr, gc_frac, &j.out->cx);
-      else
-        j.rc = packed_reads ? ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb,
-                                                      &j.out->vars, &j.out->geno, nullptr)
-                            : ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
-                                                     nullptr);  // (null: ma_process_batch)
+      // --raw-records: the batch's read arrays are made on the device first, brought back (the driver is a MA_MEM_HOST caller)
+      // and taken by the chained call from where the batch keeps them
+      auto chain = [&]() -> int {
+        if (!vcf_path.empty())  // one call: the chain with the statistics and INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
+          return ma_process_cx_batch(ctx, engine_packed ? &j.batch->packed_view : &j.batch->view, engine_packed ? &j.batch->packed : nullptr,
+                                     with_meta ? &j.batch->meta : nullptr, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
+                                     &j.out->fmt, with_meta ? &j.out->fmeta : nullptr, gc_frac, &j.out->cx);
+        if (engine_packed)
+          return ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, nullptr);
+        return ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, nullptr);  // (null: ma_process_batch)
+      };
+      j.rc = raw_records ? ma_flatten_records_batch(ctx, &j.batch->records, &j.batch->flat_out) : MA_OK;
+      if (j.rc == MA_OK) j.rc = chain();
       if (j.rc != MA_OK) j.err = ma_last_error(ctx);
       if (j.rc == MA_OK && !graphs_dir.empty()) {
         long const nf = WriteGraphs(ctx, prm, ref, *j.batch, graphs_dir);
@@ -857,7 +907,7 @@ int main(int argc, char** argv) {
       auto const tf = Clock::now();
       store.AddVariants(RecordsOfBatch(prm, *j.batch, j.out->vars, j.out->geno, as_vcf ? &j.out->cx : nullptr, true,
                                        as_vcf ? &j.out->fmt : nullptr, as_vcf ? &j.out->asmb : nullptr,
-                                       as_vcf && read_meta ? &j.out->fmeta : nullptr));
+                                       as_vcf && (read_meta || raw_records) ? &j.out->fmeta : nullptr));
       size_t const done_upto = j.batch->windows.back().genome_index + 1;
       constexpr size_t kBufferWindows = 100;
       if (done_upto > kBufferWindows && done_upto - kBufferWindows > idx_to_flush) {

@@ -24,6 +24,8 @@
  *                             body in one call
  *   ma_assemble_probe_batch <- ma_assemble_batch + the --probe-variants diagnostic: each truth allele followed through the
  *                             window's reads, raw graph, pruned graph and haplotypes (cbdg/probe_tracker.cpp)
+ *   ma_flatten_records_batch <- core::ReadCollector's sort, name interning and per-read copies (core/read_collector.cpp:42-53,
+ *                             :218-234) from raw BAM alignment records: the read arrays of a batch, made on the device
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -580,6 +582,77 @@ int ma_msa_graph_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out_t* a
  * A retried window counts in its first pass and in its retry pass.  All zero after a call with px == NULL.
  * Returns the number of entries written. */
 int ma_last_poa_export(ma_ctx_t* ctx, unsigned long long* out, int cap);
+
+/* ---- raw BAM records in, a batch's read arrays out ------------------------------------------------------------------------ */
+/* What the host shell's ReadCollector::CollectFlat does after the kept set of a window is chosen -- the collector's sort
+ * (core/read_collector.cpp:42-53), name interning, the CIGAR-derived flags and hints, the copy of every read's sequence and
+ * quality bytes into the batch layout -- on the device, from the bytes of the BAM alignment records as they sit in an inflated
+ * BGZF block.  The caller picks which records belong to which window (filters, coverage cap: its business) and lists them in
+ * arrival order; a record that falls into two windows is uploaded once and listed twice.  Nothing is dropped: read_win_off of
+ * the resulting batch IS rec_win_off, and n_reads is n_records.
+ * A RECORD is addressed by the offset of its refID field (the byte behind block_size, SAM specification 4.2) and the number of
+ * bytes available from there; these must hold the record's core -- 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq --
+ * the tags may be cut off.  Records sit at any alignment, in any order, with anything between them.  A read's name is the
+ * l_read_name - 1 bytes in front of the terminating NUL.
+ * ORDER within a window, ascending by, in turn: mapq >= 20 first; sample_rank of the record's sample; the name's bytes as
+ * unsigned chars (a proper prefix sorts first); the mapped chrom index (ref_map[rec_sample * n_refs + refID], the refID itself
+ * with ref_map == NULL, -1 for a refID outside [0, n_refs)); pos; arrival.
+ * OUTPUTS, per read in that order:
+ *   read_src       the position in rec_off of the record the read is
+ *   read_qname_id  the number of distinct names in front of the name's first appearance in the window's order; two reads share
+ *                  an id iff their names are equal byte for byte (a hash proposes, the bytes decide)
+ *   read_sample    sample_index of the record's sample
+ *   read_flags     MA_RF_PASS (mapq >= 20) | MA_RF_CASE (sample_case) | MA_RF_REV (flag 0x10)
+ *   read_hint      pos - win_start0[w] - (length of the FIRST CIGAR operation if it is S, else 0); MA_NO_HINT when the mapped
+ *                  chrom is not win_chrom[w] or the value is not inside (INT32_MIN, INT32_MAX)
+ *   read_mapq      mapq          read_isize  tlen          read_start  max(0, pos)
+ *   read_mflags    MA_RM_SOFTCLIP iff (double)(bases of all S operations) / (double)l_seq >= 0.06, | MA_RM_PROPER (flag 0x2)
+ *   read_off       the running sum of l_seq; *n_bases = read_off[n_records]
+ *   bases4         the record's (l_seq + 1) / 2 sequence bytes as they are, at byte (read_off[r] + r) >> 1: ma_packed_reads_t's
+ *                  layout with BAM's own codes; the bytes between two reads and behind the last one are zero
+ *   read_quals     the record's quality bytes at read_off[r], 0xFF (absent) as 0
+ * so that ma_batch_t {read_bases = read_quals = NULL}, ma_packed_reads_t {bases4, read_quals, 8} and ma_read_meta_t built from
+ * the same pointers go to ma_process_cx_batch / ma_process_packed_batch unchanged.
+ * ERRORS, never silent; after any of them no output but *n_bases (where stated) is defined, and none is written:
+ *   MA_ERR_ARG    a record whose core does not fit rec_len, whose rec_off + rec_len passes blob_bytes, with l_seq <= 0 or
+ *                 l_read_name == 0, or with rec_sample >= n_samples_in: ma_last_error names the first such position in rec_off.
+ *                 No kernel reads outside [blob, blob + blob_bytes), whatever a record claims
+ *   MA_ERR_ARG    *n_bases > bases_cap: *n_bases holds the need, re-submit with that capacity
+ *   MA_ERR_ARG    rec_win_off does not rise from 0 to n_records
+ *   MA_ERR_PARAM  a window of more than MA_FLATTEN_MAX_WINDOW records
+ * One 32-byte status block is read back per call; with MA_MEM_DEVICE nothing else crosses the link. */
+#define MA_FLATTEN_MAX_WINDOW 16384
+typedef struct ma_records {
+  int32_t n_windows; int64_t n_records;
+  const uint8_t*  blob;         uint64_t blob_bytes;   /* raw BAM alignment records, any alignment, any order, gaps allowed */
+  const uint64_t* rec_off;      /* [n_records] offset in blob of the record's refID field (the byte behind block_size) */
+  const uint32_t* rec_len;      /* [n_records] bytes of the record available from there (>= its core part; tags may be cut) */
+  const uint32_t* rec_win_off;  /* [n_windows + 1]; position in this list = arrival order */
+  const uint8_t*  rec_sample;   /* [n_records] index into the three sample tables below */
+  int32_t n_samples_in;         /* 1 .. 256 */
+  const uint8_t*  sample_index; /* -> read_sample */
+  const uint8_t*  sample_case;  /* 1 -> MA_RF_CASE */
+  const uint32_t* sample_rank;  /* comparator keys 2+3: order of (tag, sample name), host computed */
+  int32_t n_refs; const int32_t* ref_map; /* [n_samples_in * n_refs] BAM refID -> chrom index, NULL = identity; out of range -> -1 */
+  const int32_t*  win_chrom;    /* [n_windows] */
+  const int64_t*  win_start0;   /* [n_windows] 0-based start of the window on its contig */
+} ma_records_t;
+typedef struct ma_flat_out {    /* every member required; the ma_batch_t / ma_packed_reads_t (qual_bits 8) / ma_read_meta_t arrays */
+  uint64_t bases_cap;           /* caller's capacity of read_quals in bytes; bases4 holds (bases_cap + n_records + 1) / 2 */
+  uint64_t* n_bases;            /* [1] the NEED: sum of l_seq */
+  uint64_t* read_off;           /* [n_records + 1] */
+  uint8_t* bases4; uint8_t* read_quals;
+  uint32_t* read_qname_id; uint8_t* read_sample; uint8_t* read_flags; int32_t* read_hint;
+  uint8_t* read_mapq; uint8_t* read_mflags; int32_t* read_isize; int32_t* read_start;
+  uint32_t* read_src;           /* [n_records] which input record each output read is */
+} ma_flat_out_t;
+/* Both memory spaces: with MA_MEM_DEVICE every array of both structs is a device pointer (the structs themselves are always in
+ * host memory); with MA_MEM_HOST the inputs are uploaded and the outputs downloaded (read_quals and bases4 as far as they were
+ * written).  Single lane, like every stage call.  Eight kernels of its own (flatten.hip), which ma_last_kernel_times reports
+ * under six names: k_rec_check, k_rec_fields, k_rec_sort and k_rec_sort_large (the two instances of the sort: windows of up
+ * to 1024 records and of more), k_rec_scan (three kernels, one name), k_rec_gather; no other call runs them and this call
+ * runs no other kernel.  win_start0 must lie inside (-2^62, 2^62): the hint is computed in 64 bits. */
+int ma_flatten_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_flat_out_t* out);
 
 /* Work counters accumulated over the same region as ma_last_kernel_times (reset by ma_timing_control):
  *   out[0] read x haplotype pairs seen by ma_genotype_batch      out[1] pairs that needed the DP

@@ -279,6 +279,66 @@ def make_poa_struct(arrays, max_pnodes, max_pedges, max_cols):
     return s
 
 
+FLATTEN_MAX_WINDOW = 16384  # MA_FLATTEN_MAX_WINDOW: records per window that ma_flatten_records_batch sorts
+RECORDS_DTYPES = dict(blob=np.uint8, rec_off=np.uint64, rec_len=np.uint32, rec_win_off=np.uint32, rec_sample=np.uint8,
+                      sample_index=np.uint8, sample_case=np.uint8, sample_rank=np.uint32, ref_map=np.int32,
+                      win_chrom=np.int32, win_start0=np.int64)
+
+
+class Records(C.Structure):
+    """ma_records_t: raw BAM alignment records and which window each belongs to; ref_map may be NULL (identity)"""
+    _fields_ = [("n_windows", C.c_int32), ("n_records", C.c_int64), ("blob", C.c_void_p), ("blob_bytes", C.c_uint64),
+                ("rec_off", C.c_void_p), ("rec_len", C.c_void_p), ("rec_win_off", C.c_void_p), ("rec_sample", C.c_void_p),
+                ("n_samples_in", C.c_int32), ("sample_index", C.c_void_p), ("sample_case", C.c_void_p),
+                ("sample_rank", C.c_void_p), ("n_refs", C.c_int32), ("ref_map", C.c_void_p), ("win_chrom", C.c_void_p),
+                ("win_start0", C.c_void_p)]
+
+
+class FlatOut(C.Structure):
+    """ma_flat_out_t: the capacity, then thirteen arrays -- all required"""
+    _fields_ = [("bases_cap", C.c_uint64)] + [(n, C.c_void_p) for n in (
+        "n_bases", "read_off", "bases4", "read_quals", "read_qname_id", "read_sample", "read_flags", "read_hint", "read_mapq",
+        "read_mflags", "read_isize", "read_start", "read_src")]
+
+
+def flat_out_spec(n_records, bases_cap):
+    """arrays of ma_flat_out_t for n_records records and room for bases_cap bases (ma_flatten_records_batch)"""
+    n, B = int(n_records), int(bases_cap)
+    return dict(n_bases=(np.uint64, 1), read_off=(np.uint64, n + 1), bases4=(np.uint8, (B + n + 1) // 2),
+                read_quals=(np.uint8, B), read_qname_id=(np.uint32, n), read_sample=(np.uint8, n), read_flags=(np.uint8, n),
+                read_hint=(np.int32, n), read_mapq=(np.uint8, n), read_mflags=(np.uint8, n), read_isize=(np.int32, n),
+                read_start=(np.int32, n), read_src=(np.uint32, n))
+
+
+def records_spec(n_windows, n_records, blob_bytes, n_samples_in, n_refs=0):
+    """arrays of ma_records_t (ref_map only with n_refs > 0)"""
+    n, r, s = int(n_windows), int(n_records), int(n_samples_in)
+    spec = dict(blob=(np.uint8, int(blob_bytes)), rec_off=(np.uint64, r), rec_len=(np.uint32, r), rec_win_off=(np.uint32, n + 1),
+                rec_sample=(np.uint8, r), sample_index=(np.uint8, s), sample_case=(np.uint8, s), sample_rank=(np.uint32, s),
+                win_chrom=(np.int32, n), win_start0=(np.int64, n))
+    if n_refs > 0:
+        spec["ref_map"] = (np.int32, s * int(n_refs))
+    return spec
+
+
+def make_records_struct(arrays, n_windows, n_records, n_refs=0, blob_bytes=None):
+    """ma_records_t over a dict of arrays (numpy, torch tensors or raw pointers; kept alive by the caller).  The counts that
+    are not arguments come from the arrays where those are numpy: blob_bytes = len(blob), n_samples_in = len(sample_rank)
+    (or arrays['n_samples_in'])."""
+    s = fill_struct(Records, {k: v for k, v in arrays.items() if k in RECORDS_DTYPES})
+    s.n_windows, s.n_records, s.n_refs = int(n_windows), int(n_records), int(n_refs)
+    s.blob_bytes = int(blob_bytes if blob_bytes is not None else arrays["blob_bytes"] if "blob_bytes" in arrays else len(arrays["blob"]))
+    s.n_samples_in = int(arrays["n_samples_in"] if "n_samples_in" in arrays else len(arrays["sample_rank"]))
+    return s
+
+
+def make_flat_struct(arrays, bases_cap):
+    """ma_flat_out_t over a dict of arrays (numpy, torch tensors or raw pointers; kept alive by the caller)"""
+    s = fill_struct(FlatOut, {k: v for k, v in arrays.items() if k != "bases_cap"})
+    s.bases_cap = int(bases_cap)
+    return s
+
+
 def gate_out_spec(n):
     return dict(max_approx=(np.uint32, n), max_exact=(np.uint32, n))
 

@@ -1337,6 +1337,9 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->gx_mark.release(); ctx->gx_routes.release(); ctx->px_ctr.release();
   for (auto& bf : ctx->pb_in) bf.release();
   ctx->pb_err.release();
+  ctx->fl_ws.release();
+  for (auto& bf : ctx->fl_in) bf.release();
+  for (auto& bf : ctx->fl_out) bf.release();
   ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
@@ -1648,6 +1651,94 @@ int ma_assemble_probe_batch(ma_ctx_t* ctx, const ma_batch_t* b, const ma_asm_out
   if (ctx->memspace == MA_MEM_HOST) MA_HIP(ctx, ma_stream_sync(ctx));
   if (err & 1u) return MA_ERR_ARG;
   if (err & 2u) return MA_ERR_PARAM;
+  return MA_OK;
+}
+
+int ma_flatten_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_flat_out_t* out) {
+  MA_BEGIN(ctx);
+  if (!in || !out || in->n_windows < 0 || in->n_records < 0 || in->n_refs < 0) return MA_ERR_ARG;
+  if (in->n_samples_in < 1 || in->n_samples_in > 256) return MA_ERR_ARG;
+  if (!in->blob || !in->rec_off || !in->rec_len || !in->rec_win_off || !in->rec_sample || !in->sample_index || !in->sample_case ||
+      !in->sample_rank || !in->win_chrom || !in->win_start0)
+    return MA_ERR_ARG;
+  if (!out->n_bases || !out->read_off || !out->bases4 || !out->read_quals || !out->read_qname_id || !out->read_sample ||
+      !out->read_flags || !out->read_hint || !out->read_mapq || !out->read_mflags || !out->read_isize || !out->read_start ||
+      !out->read_src)
+    return MA_ERR_ARG;
+  if (in->n_records > 0x7FFFFFFFll) {  // (rec_win_off is 32 bits wide)
+    ma_set_err(ctx, "ma_flatten_records_batch: more than 2^31 - 1 records in one batch");
+    return MA_ERR_PARAM;
+  }
+  size_t const n = static_cast<size_t>(in->n_records), nw = static_cast<size_t>(in->n_windows), S = static_cast<size_t>(in->n_samples_in);
+  bool const host = ctx->memspace == MA_MEM_HOST;
+  ma_records_t din = *in;
+  ma_flat_out_t dout = *out;
+  // the output arrays in the struct's order, and their sizes for `bases` bases
+  struct OutItem { void** dev; void* user; size_t bytes; };
+  auto out_items = [&](u64 bases) {
+    size_t const B = static_cast<size_t>(bases);
+    return std::vector<OutItem>{
+        {reinterpret_cast<void**>(&dout.n_bases), out->n_bases, 8}, {reinterpret_cast<void**>(&dout.read_off), out->read_off, 8 * (n + 1)},
+        {reinterpret_cast<void**>(&dout.bases4), out->bases4, (B + n + 1) / 2}, {reinterpret_cast<void**>(&dout.read_quals), out->read_quals, B},
+        {reinterpret_cast<void**>(&dout.read_qname_id), out->read_qname_id, 4 * n}, {reinterpret_cast<void**>(&dout.read_sample), out->read_sample, n},
+        {reinterpret_cast<void**>(&dout.read_flags), out->read_flags, n}, {reinterpret_cast<void**>(&dout.read_hint), out->read_hint, 4 * n},
+        {reinterpret_cast<void**>(&dout.read_mapq), out->read_mapq, n}, {reinterpret_cast<void**>(&dout.read_mflags), out->read_mflags, n},
+        {reinterpret_cast<void**>(&dout.read_isize), out->read_isize, 4 * n}, {reinterpret_cast<void**>(&dout.read_start), out->read_start, 4 * n},
+        {reinterpret_cast<void**>(&dout.read_src), out->read_src, 4 * n}};
+  };
+  if (host) {
+    struct Item { const void* src; size_t bytes; const void** dst; };
+    Item const items[11] = {{in->blob, static_cast<size_t>(in->blob_bytes), reinterpret_cast<const void**>(&din.blob)},
+                            {in->rec_off, 8 * n, reinterpret_cast<const void**>(&din.rec_off)},
+                            {in->rec_len, 4 * n, reinterpret_cast<const void**>(&din.rec_len)},
+                            {in->rec_win_off, 4 * (nw + 1), reinterpret_cast<const void**>(&din.rec_win_off)},
+                            {in->rec_sample, n, reinterpret_cast<const void**>(&din.rec_sample)},
+                            {in->sample_index, S, reinterpret_cast<const void**>(&din.sample_index)},
+                            {in->sample_case, S, reinterpret_cast<const void**>(&din.sample_case)},
+                            {in->sample_rank, 4 * S, reinterpret_cast<const void**>(&din.sample_rank)},
+                            {in->ref_map, in->ref_map ? 4 * S * static_cast<size_t>(in->n_refs) : 0, reinterpret_cast<const void**>(&din.ref_map)},
+                            {in->win_chrom, 4 * nw, reinterpret_cast<const void**>(&din.win_chrom)},
+                            {in->win_start0, 8 * nw, reinterpret_cast<const void**>(&din.win_start0)}};
+    for (int i = 0; i < 11; ++i) {
+      if (!items[i].src) continue;  // (ref_map: identity)
+      MA_HIP(ctx, ctx->fl_in[i].reserve(items[i].bytes + 16));
+      if (items[i].bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->fl_in[i].p, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+      *items[i].dst = ctx->fl_in[i].p;
+    }
+    std::vector<OutItem> const oi = out_items(out->bases_cap);
+    for (size_t i = 0; i < oi.size(); ++i) {
+      MA_HIP(ctx, ctx->fl_out[i].reserve(oi[i].bytes + 16));
+      *oi[i].dev = ctx->fl_out[i].p;
+    }
+  }
+  u64 st[4] = {0, 0, 0, 0};
+  MA_TRY(launch_flatten(ctx, din, dout, st));
+  if (st[1] & 1u) {
+    ma_set_err(ctx, "ma_flatten_records_batch: rec_win_off does not rise from 0 to n_records");
+    return MA_ERR_ARG;
+  }
+  if (st[1] & 2u) {
+    ma_set_err(ctx, "ma_flatten_records_batch: window " + std::to_string(st[3]) + " holds more than " +
+                        std::to_string(MA_FLATTEN_MAX_WINDOW) + " records");
+    return MA_ERR_PARAM;
+  }
+  if (host) *out->n_bases = st[2];
+  if (st[0] != ~0ull) {
+    ma_set_err(ctx, "ma_flatten_records_batch: record " + std::to_string(st[0]) +
+                        " does not fit its rec_len or the blob, or has no bases, no name or no such sample");
+    return MA_ERR_ARG;
+  }
+  if (st[2] > out->bases_cap) {
+    ma_set_err(ctx, "ma_flatten_records_batch: the batch holds " + std::to_string(st[2]) + " bases, bases_cap is " +
+                        std::to_string(out->bases_cap));
+    return MA_ERR_ARG;
+  }
+  if (host) {
+    std::vector<OutItem> const oi = out_items(st[2]);
+    for (size_t i = 1; i < oi.size(); ++i)
+      if (oi[i].bytes) MA_HIP(ctx, hipMemcpyAsync(oi[i].user, *oi[i].dev, oi[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(ctx, ma_stream_sync(ctx));
+  }
   return MA_OK;
 }
 

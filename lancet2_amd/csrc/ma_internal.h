@@ -146,6 +146,9 @@ struct ma_ctx {
   // rounds); the device counters of that call and the counts ma_last_poa_export reports
   const ma::PoaExp* px = nullptr;
   ma::DevBuf px_ctr;
+  // ma_flatten_records_batch: its workspace (flatten.hip) and, for a MA_MEM_HOST call, the staged input and output arrays
+  ma::DevBuf fl_ws, fl_in[11], fl_out[13];
+  bool fl_lds_set = false;  // the large sort's dynamic-LDS attribute is set on this context's device
   unsigned long long poa_export_counts[4] = {0, 0, 0, 0};
   hipEvent_t sync_ev = nullptr;  // blocking-sync event: host threads sleep instead of spinning while the stream drains
   // host route (MA_MEM_HOST) of ma_process_batch, per lane: packed result records (pack.hip) and their pinned landing area
@@ -257,6 +260,11 @@ struct DPacked {
 void set_unpack_luts(DPacked* d, const ma_packed_reads_t* pk);
 // expand the reads [first, first + n) of the batch; read_off points at the entry of read `first`
 int launch_unpack(ma_ctx* ctx, const DPacked& d, const u64* read_off, u64 first, u64 n);
+
+// ma_flatten_records_batch on device pointers (flatten.hip): runs the call's kernels and waits for its status block --
+// status[0] the first bad record (~0: none), [1] bit 0 a bad rec_win_off, bit 1 a window beyond MA_FLATTEN_MAX_WINDOW,
+// [2] the bases needed, [3] the first oversized window
+int launch_flatten(ma_ctx* ctx, const ma_records_t& in, const ma_flat_out_t& out, u64* status);
 
 int launch_gate(ma_ctx* ctx, const DBatch& b, u32* max_approx, u32* max_exact);
 int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& o, const u32* gate_approx);

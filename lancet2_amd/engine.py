@@ -60,6 +60,8 @@ def load_library(path=None):
     if hasattr(lib, "ma_msa_graph_batch"):  # (likewise: a build of before the POA export)
         lib.ma_msa_graph_batch.argtypes = [C.c_void_p] * 5
         lib.ma_last_poa_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+    if hasattr(lib, "ma_flatten_records_batch"):  # (likewise: a build of before the record flattening)
+        lib.ma_flatten_records_batch.argtypes = [C.c_void_p] * 3
     return lib
 
 
@@ -198,6 +200,41 @@ class Engine:
         rc = self.lib.ma_assemble_probe_batch(self.h, C.byref(batch_struct), C.byref(asm), ref(probes), ref(probe_out))
         if rc != 0:
             e = EngineError(f"ma_assemble_probe_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+
+    def flatten_records(self, rec_arrays, n_windows, n_records, bases_cap=None, n_refs=0):
+        """ma_flatten_records_batch: raw BAM records (`rec_arrays`: the capi.RECORDS_DTYPES arrays, ref_map only with n_refs > 0)
+        -> dict of the capi.flat_out_spec arrays, cut to what was written (bases4, read_quals) + 'bases_cap'.  bases_cap None:
+        two thirds of the record bytes, which no batch of good records exceeds.  Raises EngineError with .rc = the ma_error and
+        .n_bases = the need the call reported."""
+        rec = {k: np.ascontiguousarray(rec_arrays[k], dtype=dt) for k, dt in capi.RECORDS_DTYPES.items()
+               if rec_arrays.get(k) is not None and (k != "ref_map" or n_refs > 0)}
+        if bases_cap is None:
+            bases_cap = int(rec["rec_len"][:n_records].astype(np.uint64).sum()) * 2 // 3
+        out = self._alloc(capi.flat_out_spec(n_records, bases_cap))
+        # (an empty array has no address worth passing: every member is required to be non-NULL)
+        held = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in list(rec.items()) + list(out.items())}
+        rs = capi.make_records_struct(held, n_windows, n_records, n_refs, blob_bytes=rec["blob"].size)
+        rs.n_samples_in = rec["sample_rank"].size
+        try:
+            self.flatten_records_device(rs, capi.make_flat_struct(held, bases_cap))
+        except EngineError as e:
+            e.n_bases = int(held["n_bases"][0])
+            e.arrays = out
+            raise
+        total = int(held["n_bases"][0])
+        out["n_bases"] = held["n_bases"]
+        out["bases4"] = out["bases4"][:(total + n_records + 1) // 2]
+        out["read_quals"] = out["read_quals"][:total]
+        out["bases_cap"] = int(bases_cap)
+        return out
+
+    def flatten_records_device(self, records_struct, flat_struct):
+        """ma_flatten_records_batch on caller-made structs (either memory space)"""
+        rc = self.lib.ma_flatten_records_batch(self.h, C.byref(records_struct), C.byref(flat_struct))
+        if rc != 0:
+            e = EngineError(f"ma_flatten_records_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
             e.rc = rc
             raise e
 

@@ -82,6 +82,11 @@ struct CigarUnit {
   uint32_t len;
   bool ConsumesReference() const { return op == 'M' || op == 'D' || op == 'N' || op == '=' || op == 'X'; }
 };
+inline uint64_t HashQname(std::string_view q) {  // (the reference hashes with absl; only equality of names matters)
+  uint64_t h = 1469598103934665603ull;
+  for (char c : q) h = (h ^ static_cast<uint8_t>(c)) * 1099511628211ull;
+  return h;
+}
 struct SamRecord {
   std::string qname;
   uint16_t flag = 0;
@@ -97,6 +102,28 @@ struct SamRecord {
   uint32_t l_seq4 = 0;
   bool packed = false;
   size_t SeqLen() const { return packed ? l_seq4 : seq.size(); }
+  // a BAM source opened in raw mode (--raw-records): the record's core bytes as the file has them -- the 32 fixed bytes, name,
+  // CIGAR words, packed sequence, qualities (ma_records_t's unit, include/microasm.h) -- as ONE vector
+  // per record, where the decoded record holds a name string, a CIGAR vector, a sequence and a quality vector (the bytes are
+  // copied again on their way: an indexed source's records into the collector's arena, a kept record into its window's
+  // raw_blob, the window into the batch's).  qname, cigar, seq, seq4
+  // and qual stay empty; what the filters, the coverage cap and IsActiveRegion need beyond the fixed fields is kept as scalars
+  // (the name's hash, the reference span) or read from the bytes (CIGAR words, qualities).  `packed` is set: SeqLen() is l_seq4
+  std::vector<uint8_t> raw;
+  bool is_raw = false;
+  uint64_t raw_qh = 0;    // HashQname of the name
+  int64_t raw_span = 1;   // RefSpan()
+  uint64_t NameHash() const { return is_raw ? raw_qh : HashQname(qname); }
+  size_t NumCigar() const { return is_raw ? static_cast<size_t>(raw[12] | (raw[13] << 8)) : cigar.size(); }
+  CigarUnit Cigar(size_t i) const {
+    if (!is_raw) return cigar[i];
+    static const char* kOps = "MIDNSHP=X";
+    uint32_t v;
+    std::memcpy(&v, raw.data() + 32 + raw[8] + 4 * i, 4);
+    return {(v & 15u) < 9 ? kOps[v & 15u] : '?', v >> 4};
+  }
+  const uint8_t* QualData() const { return is_raw ? raw.data() + raw.size() - l_seq4 : qual.data(); }
+  size_t QualSize() const { return is_raw ? l_seq4 : qual.size(); }
   std::vector<uint8_t> qual;
   std::string md;
   bool has_md = false, has_sa = false;
@@ -107,6 +134,7 @@ struct SamRecord {
   bool IsMappedProperPair() const { return flag & 0x2; }
   bool IsReverse() const { return flag & 0x10; }
   int64_t RefSpan() const {
+    if (is_raw) return raw_span;
     int64_t s = 0;
     for (auto const& c : cigar)
       if (c.ConsumesReference()) s += c.len;
@@ -359,7 +387,7 @@ class AlignmentSource {
             done = true;  // coordinate-sorted: nothing further in this chunk (or any later one) overlaps
             continue;
           }
-          SamRecord rec = DecodeBamRecord(buf.data(), buf.size(), ref_map_, keep_packed_);
+          SamRecord rec = DecodeBamRecord(buf.data(), buf.size(), ref_map_, keep_packed_, keep_raw_);
           if (rec.pos0 + rec.RefSpan() > s0) fn(rec);
         }
         if (done) break;
@@ -426,7 +454,9 @@ class AlignmentSource {
 
   // one BAM alignment record (SAM specification 4.2; `b` points behind its block_size field)
   // keep_packed: the sequence stays as the file has it (SamRecord::seq4: 4-bit codes, high nibble first), `seq` stays empty
-  static SamRecord DecodeBamRecord(const unsigned char* b, size_t block, std::vector<int> const& ref_map, bool keep_packed = false) {
+  // keep_raw: SamRecord's raw mode -- the core bytes in one vector, no name string, no CIGAR vector, no decoded sequence
+  static SamRecord DecodeBamRecord(const unsigned char* b, size_t block, std::vector<int> const& ref_map, bool keep_packed = false,
+                                   bool keep_raw = false) {
     static const char* kSeq = "=ACMGRSVTWYHKDBN";
     static const char* kOps = "MIDNSHP=X";
     auto rd32 = [&](size_t at) { int32_t v; std::memcpy(&v, b + at, 4); return v; };
@@ -450,25 +480,39 @@ class AlignmentSource {
     if (block < 32 || l_seq < 0 ||
         32 + static_cast<size_t>(l_read_name) + 4u * static_cast<size_t>(n_cigar) + (static_cast<size_t>(l_seq) + 1) / 2 + static_cast<size_t>(l_seq) > block)
       throw std::runtime_error("corrupt BAM record: its fields do not fit its block");
-    r.qname.assign(reinterpret_cast<const char*>(b + p), l_read_name ? l_read_name - 1u : 0u);
-    p += l_read_name;
-    for (uint16_t c = 0; c < n_cigar; ++c) {
-      uint32_t v;
-      std::memcpy(&v, b + p + 4u * c, 4);
-      r.cigar.push_back({(v & 15u) < 9 ? kOps[v & 15u] : '?', v >> 4});
-    }
-    p += 4u * n_cigar;
-    if (keep_packed) {  // copied, not decoded: the engine takes BAM's codes (ma_packed_reads_t)
-      r.seq4.assign(b + p, b + p + (static_cast<size_t>(l_seq) + 1) / 2);
+    size_t const core = 32 + static_cast<size_t>(l_read_name) + 4u * static_cast<size_t>(n_cigar) + (static_cast<size_t>(l_seq) + 1) / 2 + static_cast<size_t>(l_seq);
+    if (keep_raw) {  // the core bytes as they are, and the two scalars the collector needs of them
+      r.raw.assign(b, b + core);
+      r.is_raw = r.packed = true;
       r.l_seq4 = static_cast<uint32_t>(l_seq);
-      r.packed = true;
+      r.raw_qh = HashQname(std::string_view(reinterpret_cast<const char*>(b + p), l_read_name ? l_read_name - 1u : 0u));
+      int64_t span = 0;
+      for (size_t c = 0; c < n_cigar; ++c) {
+        CigarUnit const u = r.Cigar(c);
+        if (u.ConsumesReference()) span += u.len;
+      }
+      r.raw_span = span > 0 ? span : 1;
     } else {
-      r.seq.resize(static_cast<size_t>(l_seq));
-      for (int32_t i = 0; i < l_seq; ++i) r.seq[static_cast<size_t>(i)] = kSeq[(b[p + static_cast<size_t>(i) / 2] >> (i % 2 ? 0 : 4)) & 15];
+      r.qname.assign(reinterpret_cast<const char*>(b + p), l_read_name ? l_read_name - 1u : 0u);
+      p += l_read_name;
+      for (uint16_t c = 0; c < n_cigar; ++c) {
+        uint32_t v;
+        std::memcpy(&v, b + p + 4u * c, 4);
+        r.cigar.push_back({(v & 15u) < 9 ? kOps[v & 15u] : '?', v >> 4});
+      }
+      p += 4u * n_cigar;
+      if (keep_packed) {  // copied, not decoded: the engine takes BAM's codes (ma_packed_reads_t)
+        r.seq4.assign(b + p, b + p + (static_cast<size_t>(l_seq) + 1) / 2);
+        r.l_seq4 = static_cast<uint32_t>(l_seq);
+        r.packed = true;
+      } else {
+        r.seq.resize(static_cast<size_t>(l_seq));
+        for (int32_t i = 0; i < l_seq; ++i) r.seq[static_cast<size_t>(i)] = kSeq[(b[p + static_cast<size_t>(i) / 2] >> (i % 2 ? 0 : 4)) & 15];
+      }
+      p += static_cast<size_t>(l_seq + 1) / 2;
+      r.qual.assign(b + p, b + p + l_seq);
     }
-    p += static_cast<size_t>(l_seq + 1) / 2;
-    r.qual.assign(b + p, b + p + l_seq);
-    p += static_cast<size_t>(l_seq);
+    p = core;  // the auxiliary fields follow the core in either mode
     while (p + 3 <= block) {  // auxiliary fields: only MD:Z and the presence of SA matter here
       char const t0 = static_cast<char>(b[p]), t1 = static_cast<char>(b[p + 1]), ty = static_cast<char>(b[p + 2]);
       p += 3;
@@ -501,7 +545,7 @@ class AlignmentSource {
 
 #ifdef LANCET2_AMD_WITH_ZLIB
   // BAM: BGZF blocks are gzip members; the payload is the BAM record stream of the SAM specification, section 4.2
-  static AlignmentSource LoadBam(const std::string& path, Reference const& ref, bool keep_packed = false) {
+  static AlignmentSource LoadBam(const std::string& path, Reference const& ref, bool keep_packed = false, bool keep_raw = false) {
     std::ifstream in(path, std::ios::binary);
     if (!in) throw std::runtime_error("cannot open alignments " + path);
     std::vector<unsigned char> comp((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
@@ -545,15 +589,18 @@ class AlignmentSource {
       size_t const b = at + 4;
       at = b + static_cast<size_t>(block);
       if (at > raw.size()) break;
-      src.recs.push_back(DecodeBamRecord(raw.data() + b, static_cast<size_t>(block), ref_map, keep_packed));
+      src.recs.push_back(DecodeBamRecord(raw.data() + b, static_cast<size_t>(block), ref_map, keep_packed, keep_raw));
     }
+    src.ref_map_ = ref_map;
     src.Finish(ref.chroms.size());
     return src;
   }
   // BAM + .bai: header only; records are fetched per region (ForRegion)
-  static AlignmentSource OpenIndexedBam(const std::string& path, const std::string& bai_path, Reference const& ref, bool keep_packed = false) {
+  static AlignmentSource OpenIndexedBam(const std::string& path, const std::string& bai_path, Reference const& ref, bool keep_packed = false,
+                                        bool keep_raw = false) {
     AlignmentSource src;
     src.keep_packed_ = keep_packed;
+    src.keep_raw_ = keep_raw;
     src.index_ = std::make_shared<BamIndex>(BamIndex::Load(bai_path));
     src.path_ = path;
     src.bgzf_ = std::make_shared<BgzfFile>(path);
@@ -587,9 +634,11 @@ class AlignmentSource {
     c.ref_map_ = ref_map_;
     c.chrom_rid_ = chrom_rid_;
     c.keep_packed_ = keep_packed_;
+    c.keep_raw_ = keep_raw_;
     return c;
   }
   bool indexed() const { return bgzf_ != nullptr; }
+  std::vector<int> const& RefMap() const { return ref_map_; }  // BAM reference id -> chromosome of the FASTA
   size_t blocks_inflated() const { return bgzf_ ? bgzf_->blocks_inflated() : 0; }
 #endif
 
@@ -602,6 +651,7 @@ class AlignmentSource {
   std::string path_;
   std::vector<int> ref_map_;    // BAM reference id -> chromosome of the FASTA (-1: not in it)
   std::vector<int> chrom_rid_;  // and back
+  bool keep_raw_ = false;       // --raw-records: SamRecord's raw mode
   bool keep_packed_ = false;    // --packed-reads: records keep their sequence bytes undecoded (for ReadCollector::Params::packed_reads)
 #endif
 };
@@ -789,15 +839,9 @@ inline bool CompareReadsByPriority(Read const& l, Read const& r) {
   return l.start0 < r.start0;
 }
 
-inline uint64_t HashQname(std::string_view q) {  // (the reference hashes with absl; only equality of names matters)
-  uint64_t h = 1469598103934665603ull;
-  for (char c : q) h = (h ^ static_cast<uint8_t>(c)) * 1099511628211ull;
-  return h;
-}
-
 // ---- active region detection (core/active_region_detector.cpp:85-232) ----------------------------------------------------
 using CountMap = std::unordered_map<uint32_t, uint32_t>;
-inline bool ParseMd(std::string_view md, std::vector<uint8_t> const& quals, int64_t start, CountMap* result) {
+inline bool ParseMd(std::string_view md, const uint8_t* quals, size_t n_quals, int64_t start, CountMap* result) {
   if (start < 0) return false;
   std::string token;
   uint32_t genome_pos = static_cast<uint32_t>(start);
@@ -810,7 +854,7 @@ inline bool ParseMd(std::string_view md, std::vector<uint8_t> const& quals, int6
     genome_pos += static_cast<uint32_t>(step);
     token.clear();
     size_t const base_pos = static_cast<size_t>(genome_pos - start);
-    if (base_pos >= quals.size()) throw std::out_of_range("MD tag walks past the read");  // quals.at() in the reference
+    if (base_pos >= n_quals) throw std::out_of_range("MD tag walks past the read");  // quals.at() in the reference
     if (quals[base_pos] < 20) continue;
     char const base = static_cast<char>(std::toupper(static_cast<unsigned char>(ch)));
     if (base == 'A' || base == 'C' || base == 'T' || base == 'G') {
@@ -818,6 +862,9 @@ inline bool ParseMd(std::string_view md, std::vector<uint8_t> const& quals, int6
     }
   }
   return false;
+}
+inline bool ParseMd(std::string_view md, std::vector<uint8_t> const& quals, int64_t start, CountMap* result) {
+  return ParseMd(md, quals.data(), quals.size(), start, result);
 }
 struct MutationAccumulator {
   CountMap mismatches, insertions, deletions, softclips;
@@ -829,9 +876,11 @@ struct MutationAccumulator {
   }
   bool CheckAlignment(SamRecord const& a) {
     if (a.IsQcFail() || a.IsDuplicate() || a.IsUnmapped() || a.mapq == 0) return false;
-    if (a.has_md && ParseMd(a.md, a.qual, a.pos0, &mismatches)) return true;
+    if (a.has_md && ParseMd(a.md, a.QualData(), a.QualSize(), a.pos0, &mismatches)) return true;
     uint32_t gpos = static_cast<uint32_t>(a.pos0);
-    for (auto const& c : a.cigar) {
+    size_t const n_ops = a.NumCigar();  // (a raw-mode record: the CIGAR words of its bytes)
+    for (size_t k = 0; k < n_ops; ++k) {
+      CigarUnit const c = a.Cigar(k);
       if (c.ConsumesReference()) gpos += c.len;
       if (c.op == 'I' && ++insertions[gpos] == 2) return true;
       if (c.op == 'D' && ++deletions[gpos] == 2) return true;
@@ -840,7 +889,8 @@ struct MutationAccumulator {
     // soft clips: genome position of every clip (hts/alignment.cpp:288-361, use_padded = false)
     uint32_t ref_position = static_cast<uint32_t>(a.pos0);
     bool any = false;
-    for (auto const& c : a.cigar) {
+    for (size_t k = 0; k < n_ops; ++k) {
+      CigarUnit const c = a.Cigar(k);
       if (c.op == 'D' || c.op == 'M' || c.op == 'X' || c.op == 'N' || c.op == '=') ref_position += c.len;
       if (c.op == 'S' && ++softclips[ref_position] == 2) any = true;
     }
@@ -866,6 +916,7 @@ class ReadCollector {
   struct Params {
     double max_sample_cov = 1000.0;  // core/read_collector.h:27
     bool extract_pairs = false;
+    bool raw_records = false;   // the sources are in raw mode: CollectRaw instead of CollectFlat
     bool packed_reads = false;  // CollectFlat emits the read bases as 4-bit codes (FlatBatch::seq4) instead of letters
   };
   struct Result {
@@ -944,6 +995,18 @@ class ReadCollector {
   // holds the two paths to byte-identical batches.  Returns false when the window's options need the general path
   // (extract_pairs: out-of-region mates).
   bool CollectFlat(Window const& w, std::string_view ref_seq, struct FlatBatch* out);
+  // The same window for ma_flatten_records_batch (include/microasm.h): the same filters and the same seeded downsampling, but
+  // no sort, no interning and no per-read arrays -- `out` gets the window's scalars, its reference bases and the kept records'
+  // core bytes back to back in arrival order (FlatBatch::raw_blob: copied from the records) with their lengths and samples.  The sources must
+  // be in raw mode (SamRecord::is_raw); returns false otherwise, and when the options need the general path (extract_pairs).
+  bool CollectRaw(Window const& w, std::string_view ref_seq, struct FlatBatch* out);
+  struct Kept {
+    const SamRecord* rec;
+    uint64_t qh;
+    uint32_t sample;  // position in samples_
+    uint32_t order;   // arrival order
+  };
+  size_t SelectKept(Window const& w, std::vector<Kept>* kept, std::deque<SamRecord>* arena);
 
  private:
   Params prm_;
@@ -1011,6 +1074,22 @@ struct FlatBatch {
   // record's own bytes, SAM text packed); CopyPlaced() copies each to its place in the batch's nibble array, bases4: byte
   // (read_off[r] + r) >> 1 (include/microasm.h: ma_packed_reads_t).  Add() and Append() work on letters and refuse such a batch.
   bool packed_mode = false;
+  // raw_mode (ReadCollector::Params::raw_records, --raw-records): the batch is the INPUT of ma_flatten_records_batch
+  // (include/microasm.h: ma_records_t) -- the kept records' core bytes in raw_blob, window after window in arrival order, with
+  // rec_off / rec_len / rec_sample per record; read_win_off is rec_win_off.  The per-read arrays, read_off, read_quals and
+  // bases4 are only SIZED here (CollectRaw knows every window's bases): the call fills them (`flat_out`), and the batch then
+  // goes to the chained call as a packed one with 8-bit qualities (`packed_view`, `packed`, `meta`).  Built by CollectRaw +
+  // PlaceHeader / CopyPlaced / SizeForPlaced only, sealed by SealRaw().
+  bool raw_mode = false;
+  ByteVec raw_blob;
+  std::vector<uint64_t> rec_off;
+  std::vector<uint32_t> rec_len;
+  std::vector<uint8_t> rec_sample;
+  std::vector<int32_t> win_chrom;
+  std::vector<int64_t> win_start0;
+  uint64_t n_bases_out = 0;
+  ma_records_t records{};
+  ma_flat_out_t flat_out{};
   ByteVec seq4;
   std::vector<uint64_t> seq4_off{0};
   std::vector<uint8_t> read_sample, read_flags;
@@ -1086,13 +1165,15 @@ struct FlatBatch {
   struct Place {
     size_t ref0, read0;
     uint64_t base0;
+    size_t raw0 = 0;
   };
-  Place PlaceHeader(FlatBatch const& o) {  // o holds ONE window (what CollectFlat / Add produce)
-    Place const pl{placed_ref_, placed_reads_, placed_bases_};
+  Place PlaceHeader(FlatBatch const& o) {  // o holds ONE window (what CollectFlat / CollectRaw / Add produce)
+    Place const pl{placed_ref_, placed_reads_, placed_bases_, placed_raw_};
     windows.insert(windows.end(), o.windows.begin(), o.windows.end());
     sample_cov.insert(sample_cov.end(), o.sample_cov.begin(), o.sample_cov.end());
     placed_ref_ += o.ref_bases.size();
-    placed_reads_ += o.read_qname_id.size();
+    placed_reads_ += o.raw_mode ? o.rec_len.size() : o.read_qname_id.size();
+    placed_raw_ += o.raw_blob.size();
     placed_bases_ += o.read_off.back();
     ref_off.push_back(static_cast<uint32_t>(placed_ref_));
     read_win_off.push_back(static_cast<uint32_t>(placed_reads_));
@@ -1100,9 +1181,17 @@ struct FlatBatch {
   }
   void SizeForPlaced() {
     ref_bases.resize(placed_ref_);
-    if (packed_mode) bases4.assign(std::max<size_t>((placed_bases_ + placed_reads_ + 1) / 2, 1), 0);
-    else read_bases.resize(placed_bases_);
-    read_quals.resize(placed_bases_);
+    if (raw_mode) {  // the records, and room for what the device makes of them (the nibble array is read in aligned words)
+      raw_blob.resize(std::max<size_t>(placed_raw_, 1));
+      rec_off.resize(placed_reads_); rec_len.resize(placed_reads_); rec_sample.resize(placed_reads_);
+      bases4.resize((placed_bases_ + placed_reads_ + 1) / 2 + 8);
+      read_quals.resize(placed_bases_ + 64);
+      read_off.resize(placed_reads_ + 1);
+    } else {
+      if (packed_mode) bases4.assign(std::max<size_t>((placed_bases_ + placed_reads_ + 1) / 2, 1), 0);
+      else read_bases.resize(placed_bases_);
+      read_quals.resize(placed_bases_);
+    }
     read_sample.resize(placed_reads_);
     read_flags.resize(placed_reads_);
     read_qname_id.resize(placed_reads_);
@@ -1114,6 +1203,15 @@ struct FlatBatch {
   }
   void CopyPlaced(FlatBatch const& o, Place const& pl) {
     if (!o.ref_bases.empty()) std::memcpy(ref_bases.data() + pl.ref0, o.ref_bases.data(), o.ref_bases.size());
+    if (o.raw_mode) {
+      if (!o.raw_blob.empty()) std::memcpy(raw_blob.data() + pl.raw0, o.raw_blob.data(), o.raw_blob.size());
+      for (size_t i = 0; i < o.rec_len.size(); ++i) {
+        rec_off[pl.read0 + i] = pl.raw0 + o.rec_off[i];
+        rec_len[pl.read0 + i] = o.rec_len[i];
+        rec_sample[pl.read0 + i] = o.rec_sample[i];
+      }
+      return;
+    }
     size_t const nr = o.read_qname_id.size();
     if (nr == 0) return;
     if (packed_mode) {
@@ -1134,7 +1232,7 @@ struct FlatBatch {
     std::memcpy(read_start.data() + pl.read0, o.read_start.data(), nr * sizeof(int32_t));
     for (size_t i = 1; i <= nr; ++i) read_off[pl.read0 + i] = pl.base0 + o.read_off[i];
   }
-  size_t placed_ref_ = 0, placed_reads_ = 0;
+  size_t placed_ref_ = 0, placed_reads_ = 0, placed_raw_ = 0;
   uint64_t placed_bases_ = 0;
   // back to an empty batch that KEEPS its arrays' memory: a recycled batch does not fault 300 MB of fresh pages in again
   void Clear() {
@@ -1143,8 +1241,12 @@ struct FlatBatch {
     read_qname_id.clear(); read_hint.clear(); windows.clear(); sample_cov.clear();
     read_mapq.clear(); read_mflags.clear(); read_isize.clear(); read_start.clear();
     meta = ma_read_meta_t{};
-    placed_ref_ = placed_reads_ = 0;
+    placed_ref_ = placed_reads_ = placed_raw_ = 0;
     placed_bases_ = 0;
+    raw_blob.clear(); rec_off.clear(); rec_len.clear(); rec_sample.clear(); win_chrom.clear(); win_start0.clear();
+    records = ma_records_t{};
+    flat_out = ma_flat_out_t{};
+    n_bases_out = 0;
     seq4.clear(); seq4_off.assign(1, 0); bases4.clear(); quals_packed.clear();
     packed = ma_packed_reads_t{};
     packed_view = ma_batch_t{};
@@ -1176,6 +1278,55 @@ struct FlatBatch {
     meta.read_mapq = read_mapq.data(); meta.read_mflags = read_mflags.data();
     meta.read_isize = read_isize.data(); meta.read_start = read_start.data();
   }
+  // The sample tables and reference maps of ma_records_t: one row per sample of the collector, in its order.  Built once.
+  struct RawTables {
+    std::vector<uint8_t> index, is_case;
+    std::vector<uint32_t> rank;     // samples that tie in (tag, name) tie here, as in the comparator
+    std::vector<int32_t> ref_map;   // [samples x n_refs] BAM refID -> chrom of the FASTA, -1 beyond a file's own list
+    int32_t n_refs = 0;
+  };
+  // raw_mode, in place of Seal(): the views of ma_flatten_records_batch and of the chained call that takes its outputs
+  void SealRaw(RawTables const& t) {
+    ref_bases.resize(ref_bases.size() + 64, 0);
+    size_t const nr = rec_len.size(), nw = windows.size();
+    win_chrom.resize(nw); win_start0.resize(nw);
+    for (size_t w = 0; w < nw; ++w) {
+      win_chrom[w] = windows[w].chrom;
+      win_start0[w] = static_cast<int64_t>(windows[w].start1) - 1;
+    }
+    read_sample.resize(nr); read_flags.resize(nr); read_qname_id.resize(nr); read_hint.resize(nr);
+    read_mapq.resize(nr); read_mflags.resize(nr); read_isize.resize(nr); read_start.resize(nr);
+    read_src.resize(nr);
+    records = ma_records_t{};
+    records.n_windows = static_cast<int32_t>(nw);
+    records.n_records = static_cast<int64_t>(nr);
+    records.blob = raw_blob.data(); records.blob_bytes = placed_raw_;
+    records.rec_off = rec_off.data(); records.rec_len = rec_len.data(); records.rec_win_off = read_win_off.data();
+    records.rec_sample = rec_sample.data();
+    records.n_samples_in = static_cast<int32_t>(t.index.size());
+    records.sample_index = t.index.data(); records.sample_case = t.is_case.data(); records.sample_rank = t.rank.data();
+    records.n_refs = t.n_refs; records.ref_map = t.ref_map.data();
+    records.win_chrom = win_chrom.data(); records.win_start0 = win_start0.data();
+    flat_out = ma_flat_out_t{};
+    flat_out.bases_cap = placed_bases_;
+    flat_out.n_bases = &n_bases_out; flat_out.read_off = read_off.data();
+    flat_out.bases4 = bases4.data(); flat_out.read_quals = read_quals.data();
+    flat_out.read_qname_id = read_qname_id.data(); flat_out.read_sample = read_sample.data(); flat_out.read_flags = read_flags.data();
+    flat_out.read_hint = read_hint.data(); flat_out.read_mapq = read_mapq.data(); flat_out.read_mflags = read_mflags.data();
+    flat_out.read_isize = read_isize.data(); flat_out.read_start = read_start.data(); flat_out.read_src = read_src.data();
+    view = ma_batch_t{};
+    view.n_windows = static_cast<int32_t>(nw);
+    view.n_reads = static_cast<int64_t>(nr);
+    view.ref_bases = ref_bases.data(); view.ref_off = ref_off.data(); view.read_win_off = read_win_off.data();
+    view.read_off = read_off.data(); view.read_qname_id = read_qname_id.data(); view.read_sample = read_sample.data();
+    view.read_flags = read_flags.data(); view.read_hint = read_hint.data();
+    packed_view = view;  // (read_bases / read_quals stay null: a packed batch)
+    packed = ma_packed_reads_t{};
+    packed.bases4 = bases4.data(); packed.quals = read_quals.data(); packed.qual_bits = 8;
+    meta.read_mapq = read_mapq.data(); meta.read_mflags = read_mflags.data();
+    meta.read_isize = read_isize.data(); meta.read_start = read_start.data();
+  }
+  std::vector<uint32_t> read_src;  // raw_mode: which record each read is (ma_flat_out_t::read_src)
   // --packed-reads (include/microasm.h: ma_packed_reads_t), after Seal(): the batch's quality dictionary -- 4-bit codes into
   // the distinct Phred values in ascending order when there are at most 16 of them, the Phred bytes as they are (qual_bits =
   // 8) otherwise -- and, unless the batch was built in packed_mode (bases4 is in place then), the read bases packed from
@@ -1221,23 +1372,11 @@ struct FlatBatch {
   }
 };
 
-inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq, FlatBatch* out) {
-  if (prm_.extract_pairs) return false;
-  struct Ref {
-    const SamRecord* rec;
-    uint64_t qh;
-    uint64_t qpre;    // the name's first eight bytes, big-endian, zero-padded: its order is the names' order while it differs
-    uint32_t sample;  // position in samples_
-    uint32_t order;   // arrival order (ties of the comparator)
-  };
-  auto name_prefix = [](std::string const& q) {
-    uint64_t v = 0;
-    size_t const n = std::min<size_t>(q.size(), 8);
-    for (size_t i = 0; i < n; ++i) v |= static_cast<uint64_t>(static_cast<unsigned char>(q[i])) << (56 - 8 * i);
-    return v;
-  };
-  std::vector<Ref> kept;
-  std::deque<SamRecord> arena;  // an indexed source hands out temporaries
+// The kept set of a window, sample after sample in arrival order: the record filters and the seeded downsampling of
+// read_collector.cpp:147-216, shared by CollectFlat and CollectRaw.  Sets every sample's sampled_reads / sampled_bases and
+// returns the bases kept.  (A raw-mode record has its name's hash as a scalar: SamRecord::NameHash.)
+inline size_t ReadCollector::SelectKept(Window const& w, std::vector<Kept>* kept_out, std::deque<SamRecord>* arena) {
+  std::vector<Kept>& kept = *kept_out;
   double const max_sample_bases = prm_.max_sample_cov * static_cast<double>(w.Length());
   int64_t const s1 = static_cast<int64_t>(w.start1), e1 = static_cast<int64_t>(w.end1);
   size_t total_bases = 0;
@@ -1254,12 +1393,12 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
       if (Filtered(a)) return;
       const SamRecord* p = &a;
       if (own) {
-        arena.push_back(a);
-        p = &arena.back();
+        arena->push_back(a);
+        p = &arena->back();
       }
       n_reads += 1;
       n_bases += a.SeqLen();
-      kept.push_back(Ref{p, HashQname(a.qname), name_prefix(a.qname), static_cast<uint32_t>(si), static_cast<uint32_t>(kept.size())});
+      kept.push_back(Kept{p, a.NameHash(), static_cast<uint32_t>(si), static_cast<uint32_t>(kept.size())});
     });
     double const bases_per_read = static_cast<double>(n_bases) / static_cast<double>(std::max<uint64_t>(n_reads, 1));
     uint64_t const max_reads = static_cast<uint64_t>(std::ceil(max_sample_bases / bases_per_read));
@@ -1281,6 +1420,30 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
     sinfo.sampled_bases = bases;
     total_bases += bases;
   }
+  return total_bases;
+}
+
+inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq, FlatBatch* out) {
+  if (prm_.extract_pairs) return false;
+  struct Ref {
+    const SamRecord* rec;
+    uint64_t qh;
+    uint64_t qpre;    // the name's first eight bytes, big-endian, zero-padded: its order is the names' order while it differs
+    uint32_t sample;  // position in samples_
+    uint32_t order;   // arrival order (ties of the comparator)
+  };
+  auto name_prefix = [](std::string const& q) {
+    uint64_t v = 0;
+    size_t const n = std::min<size_t>(q.size(), 8);
+    for (size_t i = 0; i < n; ++i) v |= static_cast<uint64_t>(static_cast<unsigned char>(q[i])) << (56 - 8 * i);
+    return v;
+  };
+  std::vector<Kept> sel;
+  std::deque<SamRecord> arena;  // an indexed source hands out temporaries
+  size_t const total_bases = SelectKept(w, &sel, &arena);
+  std::vector<Ref> kept;
+  kept.reserve(sel.size());
+  for (Kept const& k : sel) kept.push_back(Ref{k.rec, k.qh, name_prefix(k.rec->qname), k.sample, k.order});
   // read_collector.cpp:42-53: filter-pass status > sample tag > sample name > qname > chrom > position (> arrival)
   std::sort(kept.begin(), kept.end(), [&](Ref const& l, Ref const& r) {
     bool const lp = l.rec->mapq >= 20, rp = r.rec->mapq >= 20;
@@ -1373,6 +1536,68 @@ inline bool ReadCollector::CollectFlat(Window const& w, std::string_view ref_seq
   }
   fb.read_win_off.push_back(static_cast<uint32_t>(fb.read_qname_id.size()));
   return true;
+}
+
+inline bool ReadCollector::CollectRaw(Window const& w, std::string_view ref_seq, FlatBatch* out) {
+  if (prm_.extract_pairs) return false;
+  std::vector<Kept> sel;
+  std::deque<SamRecord> arena;
+  size_t const total_bases = SelectKept(w, &sel, &arena);
+  size_t bytes = 0;
+  for (Kept const& k : sel) {
+    if (!k.rec->is_raw) return false;
+    bytes += k.rec->raw.size();
+  }
+  // the device sorts a window in LDS: more kept records than that (three samples at the default coverage cap of 1000x can get
+  // there) cannot go this way -- say so here, by name, instead of letting the batch fail with MA_ERR_PARAM
+  if (sel.size() > MA_FLATTEN_MAX_WINDOW)
+    throw std::runtime_error("--raw-records: window " + std::to_string(w.start1) + "-" + std::to_string(w.end1) + " keeps " +
+                             std::to_string(sel.size()) + " records, more than the " + std::to_string(MA_FLATTEN_MAX_WINDOW) +
+                             " that ma_flatten_records_batch sorts per window: lower --max-sample-cov or run without --raw-records");
+  FlatBatch& fb = *out;
+  fb.raw_mode = true;
+  fb.windows.push_back(w);
+  fb.sample_cov.emplace_back();
+  for (auto const& sm : samples_) fb.sample_cov.back().push_back(static_cast<double>(sm.sampled_bases) / static_cast<double>(w.Length()));
+  fb.ref_bases.insert(fb.ref_bases.end(), ref_seq.begin(), ref_seq.end());
+  fb.ref_off.push_back(static_cast<uint32_t>(fb.ref_bases.size()));
+  size_t const r0 = fb.rec_len.size(), b0 = fb.raw_blob.size();
+  fb.raw_blob.resize(b0 + bytes);
+  fb.rec_off.resize(r0 + sel.size()); fb.rec_len.resize(r0 + sel.size()); fb.rec_sample.resize(r0 + sel.size());
+  size_t at = b0;
+  for (size_t i = 0; i < sel.size(); ++i) {
+    std::vector<uint8_t> const& raw = sel[i].rec->raw;
+    std::memcpy(fb.raw_blob.data() + at, raw.data(), raw.size());
+    fb.rec_off[r0 + i] = at;
+    fb.rec_len[r0 + i] = static_cast<uint32_t>(raw.size());
+    fb.rec_sample[r0 + i] = static_cast<uint8_t>(sel[i].sample);
+    at += raw.size();
+  }
+  fb.read_off.push_back(fb.read_off.back() + total_bases);  // (one entry per WINDOW here: what PlaceHeader adds up)
+  fb.read_win_off.push_back(static_cast<uint32_t>(fb.rec_len.size()));
+  return true;
+}
+
+// the tables of a collector's samples (its sorted order: rec_sample is a position in it)
+inline FlatBatch::RawTables MakeRawTables(std::vector<SampleInfo> const& sorted) {
+  FlatBatch::RawTables t;
+  for (size_t i = 0; i < sorted.size(); ++i) {
+    t.index.push_back(static_cast<uint8_t>(sorted[i].index));
+    t.is_case.push_back(sorted[i].tag == Tag::CASE ? 1 : 0);
+    bool const tie = i > 0 && sorted[i].tag == sorted[i - 1].tag && sorted[i].name == sorted[i - 1].name;
+    t.rank.push_back(tie ? t.rank.back() : static_cast<uint32_t>(i));
+#ifdef LANCET2_AMD_WITH_ZLIB
+    t.n_refs = std::max(t.n_refs, static_cast<int32_t>(sorted[i].source->RefMap().size()));
+#endif
+  }
+  t.ref_map.assign(std::max<size_t>(sorted.size() * static_cast<size_t>(t.n_refs), 1), -1);
+#ifdef LANCET2_AMD_WITH_ZLIB
+  for (size_t i = 0; i < sorted.size(); ++i) {
+    std::vector<int> const& m = sorted[i].source->RefMap();
+    for (size_t r = 0; r < m.size(); ++r) t.ref_map[i * static_cast<size_t>(t.n_refs) + r] = m[r];
+  }
+#endif
+  return t;
 }
 
 // ---- the store between the workers and the output (core/variant_store.cpp) ---------------------------------------------------
