@@ -141,9 +141,13 @@ class Channel {  // bounded hand-over between two stages
   bool closed_ = false;
 };
 
+constexpr int kHostRouteFailed = -1000;  // Job::rc of a batch whose handed-back window could not be collected (no ma_error)
 struct Job {
   std::unique_ptr<FlatBatch> batch;
   std::unique_ptr<Outputs> out;
+  // --device-select: the windows ma_select_records_batch handed back (MA_S_HOST_BITS), collected by the host route and run as
+  // one-window batches of their own
+  std::vector<std::pair<std::unique_ptr<FlatBatch>, std::unique_ptr<Outputs>>> host_windows;
   int rc = MA_OK;
   std::string err;
 };
@@ -365,7 +369,7 @@ long WriteProbeResults(ma_ctx_t* ctx, const ma_params_t& prm, Reference const& r
   return written;
 }
 
-AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed, bool keep_raw) {
+AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bool keep_packed, bool keep_raw, bool keep_tags = false) {
   bool const bam = path.size() > 4 && path.substr(path.size() - 4) == ".bam";
 #ifdef LANCET2_AMD_WITH_ZLIB
   if (bam) {
@@ -373,9 +377,9 @@ AlignmentSource LoadAlignments(const std::string& path, Reference const& ref, bo
     // without one the whole file is read once
     for (std::string const& bai : {path + ".bai", path.substr(0, path.size() - 4) + ".bai"}) {
       std::ifstream probe(bai, std::ios::binary);
-      if (probe && !getenv("PIPELINE_NO_INDEX")) return AlignmentSource::OpenIndexedBam(path, bai, ref, keep_packed, keep_raw);
+      if (probe && !getenv("PIPELINE_NO_INDEX")) return AlignmentSource::OpenIndexedBam(path, bai, ref, keep_packed, keep_raw, keep_tags);
     }
-    return AlignmentSource::LoadBam(path, ref, keep_packed, keep_raw);
+    return AlignmentSource::LoadBam(path, ref, keep_packed, keep_raw, keep_tags);
   }
 #else
   if (bam) throw std::runtime_error("built without zlib (-DLANCET2_AMD_WITH_ZLIB -lz): BAM input is not available");
@@ -403,7 +407,7 @@ int main(int argc, char** argv) {
   ReadCollector::Params rp;
   ma_params_t prm;
   ma_default_params(&prm);
-  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false, poa_retry = false, raw_records = false;
+  bool no_active_region = false, extract_only = false, collect_reads = false, packed_reads = false, read_meta = false, poa_retry = false, raw_records = false, device_select = false;
   int batch_windows = 512;
   int extract_threads = static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
   for (int i = 1; i < argc; ++i) {
@@ -438,6 +442,7 @@ int main(int argc, char** argv) {
     else if (a == "--collect-reads") collect_reads = true;  // the reference-shaped collector (a Read per alignment) instead of CollectFlat
     else if (a == "--packed-reads") packed_reads = true;  // 4-bit read bases (and qualities) to the engine: ma_process_packed_batch
     else if (a == "--raw-records") raw_records = true;  // BAM records as they are to the engine: ma_flatten_records_batch, then the chained call
+    else if (a == "--device-select") device_select = true;  // with --raw-records: filters, active-region detection and coverage gates on the device
     else if (a == "--read-meta") read_meta = true;  // with --out-vcf: the six FORMAT statistics over the read metadata too
     else if (a == "--poa-retry") poa_retry = true;  // ma_set_poa_retry: a second POA pass over the windows whose graph overflowed
     else if (a == "--extract-only") extract_only = true;  // stage 1 alone (with --dump): no device needed
@@ -468,6 +473,13 @@ int main(int argc, char** argv) {
                          "  --raw-records   BAM inputs only: the kept records go to the engine as the file has them; ma_flatten_records_batch\n"
                          "                  sorts them, interns the names and lays out the bases, then the chained call runs as with\n"
                          "                  --packed-reads --read-meta.  With --extract-only --dump: the ma_records_t arrays\n"
+                         "  --device-select with --raw-records: every candidate record of a window goes to the engine, whole block, tags included;\n"
+                         "                  ma_select_records_batch applies the record filters, detects the active regions and gates on\n"
+                         "                  coverage, ma_flatten_records_batch takes the selected lists.  The N-only and repeat gates stay on the\n"
+                         "                  host; a window the call hands back (coverage cap, an MD string that leaves its read, a full event\n"
+                         "                  table) is collected by the host route and run as a batch of its own -- on the engine thread, one\n"
+                         "                  window at a time, while the device waits: meant for the few windows of ordinary depth, not for\n"
+                         "                  data where most windows are capped (raise --max-sample-cov or run without the flag)\n"
                          "  --read-meta     with --out-vcf: MAPQ, soft-clip and proper-pair flags, insert size and start of every read go to the\n"
                          "                  engine beside the batch (ma_process_meta_batch) and RMQ, SCA, FLD, RPCD, MQCD and FSSE are printed:\n"
                          "                  all 24 FORMAT values.  Without it those six are \".\"\n"
@@ -485,6 +497,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "pipeline_driver: --raw-records hands BAM records to the engine; %s is not a BAM file\n", path.c_str());
         return 2;
       }
+  if (device_select && !raw_records) {
+    std::fprintf(stderr, "pipeline_driver: --device-select selects among raw records on the device (needs --raw-records)\n");
+    return 2;
+  }
   if (raw_records && (!graphs_dir.empty() || !probe_variants_path.empty() || !msa_dir.empty())) {  // (stage calls on ASCII reads)
     std::fprintf(stderr, "pipeline_driver: --out-graphs-dir / --probe-variants / --out-msa-dir need ASCII reads (not with --raw-records)\n");
     return 2;
@@ -516,7 +532,7 @@ int main(int argc, char** argv) {
   sources.reserve(normals.size() + tumors.size());
   std::vector<SampleInfo> samples;
   auto add_sample = [&](const std::string& path, Tag tag) {
-    sources.push_back(LoadAlignments(path, ref, packed_reads, raw_records));  // (packed: BAM records keep their sequence bytes)
+    sources.push_back(LoadAlignments(path, ref, packed_reads, raw_records, device_select));  // (packed: BAM records keep their sequence bytes)
     std::string name = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
     name = name.substr(0, name.find_last_of('.'));
     samples.push_back({name, tag, nullptr, 0, 0, 0});
@@ -656,8 +672,13 @@ int main(int argc, char** argv) {
         Window const& w = windows[i];
         std::string_view const seq(ref.chroms[static_cast<size_t>(w.chrom)].seq.data() + (w.start1 - 1), w.Length());
         Slot& sl = slots[i];
-        sl.st = PreReadGate(seq, prm.max_k, no_active_region, collector.Samples(), w);
-        if (sl.st == WindowStatus::RUN) {
+        // --device-select: the N-only and repeat gates here, the rest of the gate on the device
+        sl.st = PreReadGate(seq, prm.max_k, no_active_region || device_select, collector.Samples(), w);
+        if (sl.st == WindowStatus::RUN && device_select) {
+          auto flat = std::make_unique<FlatBatch>();
+          if (!collector.CollectCandidates(w, seq, flat.get())) throw std::runtime_error("--device-select: a source is not in raw mode");
+          sl.flat = std::move(flat);
+        } else if (sl.st == WindowStatus::RUN) {
           // the window's reads straight into its flat arrays (ReadCollector::CollectFlat); the reference-shaped path -- a Read
           // per alignment, then FlatBatch::Add -- when the options need it (--extract-pairs) or --collect-reads asks for it
           auto flat = std::make_unique<FlatBatch>();
@@ -726,7 +747,9 @@ int main(int argc, char** argv) {
         auto const ts = Clock::now();
         Job j = std::move(pending.front().job);
         pending.pop_front();
-        if (raw_records) {
+        if (device_select) {
+          j.batch->SealCandidates(raw_tables, rp.max_sample_cov, static_cast<uint32_t>(std::max(0, prm.min_anchor_cov)), no_active_region);
+        } else if (raw_records) {
           j.batch->SealRaw(raw_tables);
         } else {
           j.batch->Seal();
@@ -813,7 +836,22 @@ int main(int argc, char** argv) {
     if (!probe_out) { std::perror("--probe-results"); return 4; }
     std::fputs(kProbeResultsHeader, probe_out);
   }
+  // --device-select: the host route of the windows the device hands back runs on the engine thread, with sources of its own
+  std::vector<SampleInfo> engine_samples = samples;
+  std::vector<AlignmentSource> engine_clones;
+#ifdef LANCET2_AMD_WITH_ZLIB
+  if (device_select) {
+    engine_clones.reserve(engine_samples.size());
+    for (auto& sm : engine_samples)
+      if (sm.source->indexed()) {
+        engine_clones.push_back(sm.source->CloneIndexed());
+        sm.source = &engine_clones.back();
+      }
+  }
+#endif
+  size_t n_host_windows = 0;
   std::thread engine([&] {
+    ReadCollector host_collector(rp, engine_samples);
     Job j;
     while (to_engine.Pop(&j)) {
       if (extract_only) {
@@ -832,18 +870,66 @@ int main(int argc, char** argv) {
       j.out->Allocate(prm, j.batch->view.n_windows, !vcf_path.empty(), with_meta);
       // --raw-records: the batch's read arrays are made on the device first, brought back (the driver is a MA_MEM_HOST caller)
       // and taken by the chained call from where the batch keeps them
-      auto chain = [&]() -> int {
+      auto chain = [&](FlatBatch& fb, Outputs& o) -> int {
         if (!vcf_path.empty())  // one call: the chain with the statistics and INFO SEQ_CX / GRAPH_CX (core/variant_builder.cpp:159-160)
-          return ma_process_cx_batch(ctx, engine_packed ? &j.batch->packed_view : &j.batch->view, engine_packed ? &j.batch->packed : nullptr,
-                                     with_meta ? &j.batch->meta : nullptr, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno,
-                                     &j.out->fmt, with_meta ? &j.out->fmeta : nullptr, gc_frac, &j.out->cx);
+          return ma_process_cx_batch(ctx, engine_packed ? &fb.packed_view : &fb.view, engine_packed ? &fb.packed : nullptr,
+                                     with_meta ? &fb.meta : nullptr, &o.gate, &o.asmb, &o.vars, &o.geno,
+                                     &o.fmt, with_meta ? &o.fmeta : nullptr, gc_frac, &o.cx);
         if (engine_packed)
-          return ma_process_packed_batch(ctx, &j.batch->packed_view, &j.batch->packed, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, nullptr);
-        return ma_process_stats_batch(ctx, &j.batch->view, &j.out->gate, &j.out->asmb, &j.out->vars, &j.out->geno, nullptr);  // (null: ma_process_batch)
+          return ma_process_packed_batch(ctx, &fb.packed_view, &fb.packed, &o.gate, &o.asmb, &o.vars, &o.geno, nullptr);
+        return ma_process_stats_batch(ctx, &fb.view, &o.gate, &o.asmb, &o.vars, &o.geno, nullptr);  // (null: ma_process_batch)
       };
-      j.rc = raw_records ? ma_flatten_records_batch(ctx, &j.batch->records, &j.batch->flat_out) : MA_OK;
-      if (j.rc == MA_OK) j.rc = chain();
+      // --device-select: the candidates' record bits, the windows' states and the selected lists first; the flatten call and
+      // the chain then see the selected records alone (a window that is not listed has none: nothing is made of it)
+      if (device_select) {
+        j.rc = ma_select_records_batch(ctx, &j.batch->records, &j.batch->sel_params, &j.batch->sel_out);
+        if (j.rc == MA_OK) j.batch->UseSelected();
+      }
+      // (a batch of which nothing is listed has no read at all: there is nothing to flatten or to assemble, its outputs stay
+      // as Allocate() made them -- no variant anywhere)
+      bool const nothing_listed = device_select && j.rc == MA_OK && j.batch->n_selected == 0;
+      if (nothing_listed)
+        for (int w = 0; w < j.batch->view.n_windows; ++w) j.out->asmb.win_status[w] = MA_W_NO_HAPLOTYPE;
+      if (j.rc == MA_OK && raw_records && !nothing_listed) j.rc = ma_flatten_records_batch(ctx, &j.batch->records, &j.batch->flat_out);
+      if (j.rc == MA_OK && !nothing_listed) j.rc = chain(*j.batch, *j.out);
       if (j.rc != MA_OK) j.err = ma_last_error(ctx);
+      for (size_t w = 0; device_select && j.rc == MA_OK && w < j.batch->windows.size(); ++w) {
+        if (!(j.batch->win_state[w] & MA_S_HOST_BITS)) continue;
+        // handed back: today's route for this window -- PreReadGate, CollectRaw with its downsampling, the coverage gate -- and
+        // a batch of its own
+        Window const& win = j.batch->windows[w];
+        std::string_view const seq(ref.chroms[static_cast<size_t>(win.chrom)].seq.data() + (win.start1 - 1), win.Length());
+        ++n_host_windows;
+        try {
+          if (PreReadGate(seq, prm.max_k, no_active_region, host_collector.Samples(), win) != WindowStatus::RUN) {
+            j.batch->win_state[w] = static_cast<uint8_t>(j.batch->win_state[w] & ~MA_S_ACTIVE);  // (for the counts below)
+            continue;
+          }
+          FlatBatch one;
+          if (!host_collector.CollectRaw(win, seq, &one)) throw std::runtime_error("--device-select: a source is not in raw mode");
+          if (CrossSampleMeanCoverage(host_collector.Samples(), win.Length()) < static_cast<double>(prm.min_anchor_cov)) {
+            j.batch->win_state[w] = static_cast<uint8_t>(j.batch->win_state[w] | MA_S_ACTIVE | MA_S_LOW_COVERAGE);
+            continue;
+          }
+          j.batch->win_state[w] = static_cast<uint8_t>((j.batch->win_state[w] | MA_S_ACTIVE) & ~MA_S_LOW_COVERAGE);
+          auto hb = std::make_unique<FlatBatch>();
+          hb->raw_mode = true;
+          FlatBatch::Place const pl = hb->PlaceHeader(one);
+          hb->SizeForPlaced();
+          hb->CopyPlaced(one, pl);
+          hb->SealRaw(raw_tables);
+          auto ho = std::make_unique<Outputs>();
+          ho->Allocate(prm, 1, !vcf_path.empty(), with_meta);
+          j.rc = ma_flatten_records_batch(ctx, &hb->records, &hb->flat_out);
+          if (j.rc == MA_OK) j.rc = chain(*hb, *ho);
+          if (j.rc != MA_OK) j.err = ma_last_error(ctx);
+          j.host_windows.emplace_back(std::move(hb), std::move(ho));
+        } catch (std::exception const& e) {  // (reading the alignments failed: not an engine error, the batch fails all the same)
+          j.rc = kHostRouteFailed;
+          j.err = std::string("--device-select: the host route of window ") + std::to_string(win.start1) + "-" + std::to_string(win.end1) +
+                  " failed: " + e.what();
+        }
+      }
       if (j.rc == MA_OK && !graphs_dir.empty()) {
         long const nf = WriteGraphs(ctx, prm, ref, *j.batch, graphs_dir);
         if (nf < 0) {
@@ -887,6 +973,7 @@ int main(int argc, char** argv) {
   if (as_vcf) std::fputs(VcfHeader(ref, sorted_samples, prm.case_ctrl_mode != 0, true, command_line, ref_path).c_str(), out);
   VariantStore store;
   size_t n_records = 0, n_assembled = 0, n_flagged = 0, idx_to_flush = 0;
+  size_t n_dev_skipped[5] = {0, 0, 0, 0, 0};  // --device-select: windows the device call (or the host route behind it) skipped
   int rc_all = 0;
   auto write = [&](std::vector<VariantRecord> recs) {
     for (auto const& r : recs)
@@ -905,9 +992,17 @@ int main(int argc, char** argv) {
       // call can still be replaced by a better covered duplicate from a window that overlaps its own (batches finish in
       // window order here; windows the gates skipped count as done)
       auto const tf = Clock::now();
-      store.AddVariants(RecordsOfBatch(prm, *j.batch, j.out->vars, j.out->geno, as_vcf ? &j.out->cx : nullptr, true,
-                                       as_vcf ? &j.out->fmt : nullptr, as_vcf ? &j.out->asmb : nullptr,
-                                       as_vcf && (read_meta || raw_records) ? &j.out->fmeta : nullptr));
+      auto records_of = [&](FlatBatch const& fb, Outputs const& o) {
+        return RecordsOfBatch(prm, fb, o.vars, o.geno, as_vcf ? &o.cx : nullptr, true, as_vcf ? &o.fmt : nullptr, as_vcf ? &o.asmb : nullptr,
+                              as_vcf && (read_meta || raw_records) ? &o.fmeta : nullptr);
+      };
+      std::vector<VariantRecord> recs = records_of(*j.batch, *j.out);
+      if (!j.host_windows.empty()) {  // the handed-back windows' records where the batch would have had them: in window order
+        for (auto const& hw : j.host_windows)
+          for (auto& r : records_of(*hw.first, *hw.second)) recs.push_back(std::move(r));
+        std::stable_sort(recs.begin(), recs.end(), [](VariantRecord const& a, VariantRecord const& b) { return a.window_index < b.window_index; });
+      }
+      store.AddVariants(std::move(recs));
       size_t const done_upto = j.batch->windows.back().genome_index + 1;
       constexpr size_t kBufferWindows = 100;
       if (done_upto > kBufferWindows && done_upto - kBufferWindows > idx_to_flush) {
@@ -915,7 +1010,18 @@ int main(int argc, char** argv) {
         write(store.ExtractBeforeWindow(windows[idx_to_flush]));
       }
       for (int w = 0; w < j.batch->view.n_windows; ++w) {
+        if (device_select && !(j.batch->win_state[static_cast<size_t>(w)] & MA_S_LISTED)) {  // skipped on the device, or run by the host route
+          uint8_t const ws = j.batch->win_state[static_cast<size_t>(w)];
+          if (!(ws & MA_S_ACTIVE)) n_dev_skipped[3]++;
+          else if (ws & MA_S_LOW_COVERAGE) n_dev_skipped[4]++;
+          continue;
+        }
         uint32_t const st = j.out->asmb.win_status[w];
+        n_assembled += (st & MA_W_NO_HAPLOTYPE) ? 0 : 1;
+        n_flagged += (st & ~static_cast<uint32_t>(MA_W_NO_HAPLOTYPE | MA_W_BFS_LIMIT)) ? 1 : 0;
+      }
+      for (auto const& hw : j.host_windows) {
+        uint32_t const st = hw.second->asmb.win_status[0];
         n_assembled += (st & MA_W_NO_HAPLOTYPE) ? 0 : 1;
         n_flagged += (st & ~static_cast<uint32_t>(MA_W_NO_HAPLOTYPE | MA_W_BFS_LIMIT)) ? 1 : 0;
       }
@@ -944,7 +1050,9 @@ int main(int argc, char** argv) {
   std::fprintf(stderr,
                "pipeline_driver: %zu windows (%zu N-only, %zu max-k repeat, %zu inactive, %zu below anchor coverage), %zu assembled, "
                "%zu with a capacity flag, %zu records\n",
-               windows.size(), n_skipped[1], n_skipped[2], n_skipped[3], n_skipped[4], n_assembled, n_flagged, n_records);
+               windows.size(), n_skipped[1], n_skipped[2], n_skipped[3] + n_dev_skipped[3], n_skipped[4] + n_dev_skipped[4], n_assembled, n_flagged,
+               n_records);
+  if (device_select) std::fprintf(stderr, "pipeline_driver: --device-select handed %zu windows back to the host route\n", n_host_windows);
   if (probe_out) {
     std::fclose(probe_out);
     std::fprintf(stderr, "pipeline_driver: %zu probe records of %zu truth variants written to %s (%zu activations skipped: an allele past its window or the call's limits)\n",

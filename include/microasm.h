@@ -26,6 +26,10 @@
  *                             window's reads, raw graph, pruned graph and haplotypes (cbdg/probe_tracker.cpp)
  *   ma_flatten_records_batch <- core::ReadCollector's sort, name interning and per-read copies (core/read_collector.cpp:42-53,
  *                             :218-234) from raw BAM alignment records: the read arrays of a batch, made on the device
+ *   ma_select_records_batch <- the record filters and per-sample sums of core::ReadCollector (core/read_collector.cpp:147-216),
+ *                             core::ActiveRegionDetector (core/active_region_detector.cpp:85-232) and the anchor-coverage gate
+ *                             (core/variant_builder.cpp:214-224) on every candidate record of a window: which records go on,
+ *                             as the lists ma_flatten_records_batch takes
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -653,6 +657,90 @@ typedef struct ma_flat_out {    /* every member required; the ma_batch_t / ma_pa
  * to 1024 records and of more), k_rec_scan (three kernels, one name), k_rec_gather; no other call runs them and this call
  * runs no other kernel.  win_start0 must lie inside (-2^62, 2^62): the hint is computed in 64 bits. */
 int ma_flatten_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_flat_out_t* out);
+
+/* ---- which records of a window go on: filters, active-region detection, coverage gates ------------------------------------- */
+/* What the host shell does per window BEFORE the kept set is known -- MutationAccumulator::CheckAlignment over every record
+ * (core/active_region_detector.cpp:85-232), ReadCollector::Filtered and the per-sample sums of SelectKept
+ * (core/read_collector.cpp:147-216), the anchor-coverage gate (core/variant_builder.cpp:214-224) -- on the device, from the
+ * same record bytes.  `in` is ma_records_t read differently: per window it lists the CANDIDATES, every record the host's
+ * ForRegion would visit for that window, for every sample, in arrival order and unfiltered; rec_len covers the auxiliary
+ * fields (as far as the caller has them: tags cut off anywhere end the walk there).  sample_index, sample_case, sample_rank,
+ * ref_map, win_chrom and win_start0 are not read and may be NULL.
+ * RECORD BITS (rec_keep, one byte per candidate):
+ *   MA_SK_COLLECT   none of flag 0x200, 0x400, 0x4 is set and mapq >= 20: what ReadCollector::Filtered lets through
+ *   MA_SK_ELIGIBLE  none of those three flags is set and mapq != 0: what CheckAlignment looks at
+ * EVENTS.  An eligible record adds events to four multisets of 32-bit positions -- mismatches, insertions, deletions,
+ * softclips -- kept per (window, sample).  All position arithmetic is modulo 2^32 and starts from (uint32_t)pos.
+ *   MD     if pos >= 0 and the auxiliary fields hold an MD field of type Z.  The fields are walked from the end of the core:
+ *          two tag bytes, a type byte, then A c C: 1 byte; s S: 2; i I f: 4; Z H: up to and with the NUL; B: a subtype byte, an
+ *          int32 count, count elements of 1 (c C), 2 (s S) or 4 (any other subtype) bytes.  The walk ends at an unknown type, a
+ *          negative count, a string without NUL, a field that passes rec_len, or with fewer than 3 bytes left.  The LAST MD:Z
+ *          found wins.  Its bytes are read in turn: a digit extends the pending number; any other byte first advances the
+ *          position by the pending number (none: 0), then looks at qual[position - (uint32_t)pos]: an index >= l_seq, or a
+ *          pending number of more than 9 digits, sets MA_S_MD_RANGE on the window and ends this record's MD walk (the host
+ *          throws there -- and whether it gets that far depends on the record order); a quality under 20 skips the byte;
+ *          otherwise the byte, upper-cased, adds a MISMATCH event at the position if it is A, C, G or T.  So the letters
+ *          behind '^' land on one position, the quality index ignores clips and insertions, and absent (0xFF) qualities pass.
+ *   CIGAR  a running position advances by the length of every M, D, N, = and X.  AFTER the advance an I adds an INSERTION
+ *          event, a D a DELETION event, an X a MISMATCH event (the multiset of the MD mismatches) at the position; an S adds
+ *          a SOFTCLIP event at the position reached so far.
+ * WINDOW STATE (win_state, one byte per window):
+ *   MA_S_ACTIVE        some sample has, in one multiset, a position with two or more events -- the host's early returns only
+ *                      skip work once that is known to be so, whatever the record order.  With skip_active_region every window
+ *                      is active and no event is looked at: MA_S_MD_RANGE and MA_S_EVENTS are never set then
+ *   MA_S_CAPPED        for some sample with reads: reads > ceil(max_sample_cov * win_len / (bases / reads)), in f64 -- the host
+ *                      would downsample (a seeded std::shuffle: host business)
+ *   MA_S_LOW_COVERAGE  (double)(sum of bases over the samples) / (double)win_len < (double)min_anchor_cov; meaningless when
+ *                      the window is capped (the host's sum is taken after the downsampling)
+ *   MA_S_MD_RANGE      see MD
+ *   MA_S_EVENTS        no position reached two and a (window, sample) held more than MA_SELECT_EVENT_KEYS distinct (multiset,
+ *                      position) keys: the kernel's table was full.  (With more keys than that AND a position that reaches
+ *                      two, the window is reported MA_S_ACTIVE or MA_S_EVENTS, whichever the kernel met first; either is true
+ *                      to the host's answer, since the caller settles an MA_S_EVENTS window itself)
+ *   MA_S_LISTED        active, none of CAPPED, MD_RANGE, EVENTS, and not LOW_COVERAGE: the window's MA_SK_COLLECT records are
+ *                      in the selected lists.  Every other window has an empty sel_win_off range; for one with any of
+ *                      MA_S_HOST_BITS the caller does the selection itself, the others are skipped windows (inactive: not
+ *                      MA_S_ACTIVE; else low coverage)
+ * reads and bases above are win_sample_reads / win_sample_bases: the count and the sum of l_seq of the window's MA_SK_COLLECT
+ * records per sample -- SampleInfo::sampled_reads / sampled_bases of an uncapped window.
+ * SELECTED LISTS.  n_selected, sel_win_off and, per selected record in window order and arrival order within the window,
+ * sel_off / sel_len / sel_sample (rec_off, rec_len, rec_sample of the candidate) and sel_src (its position in rec_off), so that
+ * ma_records_t{n_windows, *n_selected, blob, blob_bytes, sel_off, sel_len, sel_win_off, sel_sample, ... the rest of `in`} goes to
+ * ma_flatten_records_batch unchanged.  The four sel_ arrays are sized n_records by the caller.
+ * ERRORS, never silent; after any of them no output is defined, and none is written:
+ *   MA_ERR_ARG    a record whose core does not fit rec_len, whose rec_off + rec_len passes blob_bytes, with l_seq <= 0 or
+ *                 l_read_name == 0, or with rec_sample >= n_samples_in: ma_last_error names the first such position in rec_off.
+ *                 No kernel reads outside [blob, blob + blob_bytes), whatever a record claims
+ *   MA_ERR_ARG    rec_win_off does not rise from 0 to n_records; a NULL member of `sp` or `out`
+ * Both memory spaces like ma_flatten_records_batch; one 32-byte status block is read back per call, with MA_MEM_DEVICE nothing
+ * else crosses the link.  Five kernels of its own (select.hip), reported by ma_last_kernel_times as k_sel_check, k_sel_fields,
+ * k_sel_window, k_sel_scan, k_sel_gather; no other call runs them and this call runs no other kernel. */
+#define MA_SK_COLLECT 1
+#define MA_SK_ELIGIBLE 2
+#define MA_S_ACTIVE 1
+#define MA_S_LOW_COVERAGE 2
+#define MA_S_CAPPED 4
+#define MA_S_MD_RANGE 8
+#define MA_S_EVENTS 16
+#define MA_S_LISTED 32
+#define MA_S_HOST_BITS (MA_S_CAPPED | MA_S_MD_RANGE | MA_S_EVENTS)
+#define MA_SELECT_EVENT_KEYS 8192 /* distinct (multiset, position) keys a (window, sample) may hold */
+typedef struct ma_select_params {
+  double max_sample_cov;        /* ReadCollector::Params::max_sample_cov */
+  uint32_t min_anchor_cov;
+  int32_t skip_active_region;   /* != 0: every window is active */
+  const uint32_t* win_len;      /* [n_windows] Window::Length() */
+} ma_select_params_t;
+typedef struct ma_select_out {  /* every member required */
+  uint8_t* rec_keep;            /* [n_records] MA_SK_* */
+  uint8_t* win_state;           /* [n_windows] MA_S_* */
+  uint32_t* win_sample_reads;   /* [n_windows * n_samples_in] */
+  uint64_t* win_sample_bases;   /* [n_windows * n_samples_in] */
+  uint64_t* n_selected;         /* [1] */
+  uint32_t* sel_win_off;        /* [n_windows + 1] */
+  uint64_t* sel_off; uint32_t* sel_len; uint8_t* sel_sample; uint32_t* sel_src;  /* [n_records] each, *n_selected written */
+} ma_select_out_t;
+int ma_select_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_select_params_t* sp, const ma_select_out_t* out);
 
 /* Work counters accumulated over the same region as ma_last_kernel_times (reset by ma_timing_control):
  *   out[0] read x haplotype pairs seen by ma_genotype_batch      out[1] pairs that needed the DP

@@ -339,6 +339,40 @@ def make_flat_struct(arrays, bases_cap):
     return s
 
 
+MA_SK_COLLECT, MA_SK_ELIGIBLE = 1, 2
+MA_S_ACTIVE, MA_S_LOW_COVERAGE, MA_S_CAPPED, MA_S_MD_RANGE, MA_S_EVENTS, MA_S_LISTED = 1, 2, 4, 8, 16, 32
+MA_S_HOST_BITS = MA_S_CAPPED | MA_S_MD_RANGE | MA_S_EVENTS
+SELECT_EVENT_KEYS = 8192  # MA_SELECT_EVENT_KEYS: distinct (multiset, position) keys of one (window, sample)
+SELECT_IN_KEYS = ("blob", "rec_off", "rec_len", "rec_win_off", "rec_sample")  # what ma_select_records_batch reads of ma_records_t
+
+
+class SelectParams(C.Structure):
+    """ma_select_params_t"""
+    _fields_ = [("max_sample_cov", C.c_double), ("min_anchor_cov", C.c_uint32), ("skip_active_region", C.c_int32),
+                ("win_len", C.c_void_p)]
+
+
+class SelectOut(C.Structure):
+    """ma_select_out_t: ten arrays -- all required"""
+    _fields_ = [(n, C.c_void_p) for n in ("rec_keep", "win_state", "win_sample_reads", "win_sample_bases", "n_selected",
+                                          "sel_win_off", "sel_off", "sel_len", "sel_sample", "sel_src")]
+
+
+def select_out_spec(n_windows, n_records, n_samples_in):
+    """arrays of ma_select_out_t (ma_select_records_batch)"""
+    n, r, s = int(n_windows), int(n_records), int(n_samples_in)
+    return dict(rec_keep=(np.uint8, r), win_state=(np.uint8, n), win_sample_reads=(np.uint32, n * s),
+                win_sample_bases=(np.uint64, n * s), n_selected=(np.uint64, 1), sel_win_off=(np.uint32, n + 1),
+                sel_off=(np.uint64, r), sel_len=(np.uint32, r), sel_sample=(np.uint8, r), sel_src=(np.uint32, r))
+
+
+def make_select_params(win_len, max_sample_cov=1000.0, min_anchor_cov=5, skip_active_region=False):
+    """ma_select_params_t; win_len: a numpy array, a torch tensor or a raw pointer (kept alive by the caller)"""
+    s = fill_struct(SelectParams, dict(win_len=win_len))
+    s.max_sample_cov, s.min_anchor_cov, s.skip_active_region = float(max_sample_cov), int(min_anchor_cov), int(bool(skip_active_region))
+    return s
+
+
 def gate_out_spec(n):
     return dict(max_approx=(np.uint32, n), max_exact=(np.uint32, n))
 

@@ -1340,6 +1340,9 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->fl_ws.release();
   for (auto& bf : ctx->fl_in) bf.release();
   for (auto& bf : ctx->fl_out) bf.release();
+  ctx->sl_ws.release();
+  for (auto& bf : ctx->sl_in) bf.release();
+  for (auto& bf : ctx->sl_out) bf.release();
   ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
@@ -1736,6 +1739,80 @@ int ma_flatten_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_fla
   if (host) {
     std::vector<OutItem> const oi = out_items(st[2]);
     for (size_t i = 1; i < oi.size(); ++i)
+      if (oi[i].bytes) MA_HIP(ctx, hipMemcpyAsync(oi[i].user, *oi[i].dev, oi[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(ctx, ma_stream_sync(ctx));
+  }
+  return MA_OK;
+}
+
+int ma_select_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_select_params_t* sp, const ma_select_out_t* out) {
+  MA_BEGIN(ctx);
+  if (!in || !sp || !out || in->n_windows < 0 || in->n_records < 0) return MA_ERR_ARG;
+  if (in->n_samples_in < 1 || in->n_samples_in > 256) return MA_ERR_ARG;
+  if (!in->blob || !in->rec_off || !in->rec_len || !in->rec_win_off || !in->rec_sample || !sp->win_len) return MA_ERR_ARG;
+  if (!out->rec_keep || !out->win_state || !out->win_sample_reads || !out->win_sample_bases || !out->n_selected || !out->sel_win_off ||
+      !out->sel_off || !out->sel_len || !out->sel_sample || !out->sel_src)
+    return MA_ERR_ARG;
+  if (in->n_records > 0x7FFFFFFFll) {  // (rec_win_off is 32 bits wide)
+    ma_set_err(ctx, "ma_select_records_batch: more than 2^31 - 1 records in one batch");
+    return MA_ERR_PARAM;
+  }
+  size_t const n = static_cast<size_t>(in->n_records), nw = static_cast<size_t>(in->n_windows), S = static_cast<size_t>(in->n_samples_in);
+  bool const host = ctx->memspace == MA_MEM_HOST;
+  ma_records_t din = *in;
+  ma_select_params_t dsp = *sp;
+  ma_select_out_t dout = *out;
+  // the output arrays in the struct's order, and their sizes with `sel` records selected
+  struct OutItem { void** dev; void* user; size_t bytes; };
+  auto out_items = [&](u64 sel) {
+    size_t const L = static_cast<size_t>(sel);
+    return std::vector<OutItem>{
+        {reinterpret_cast<void**>(&dout.rec_keep), out->rec_keep, n}, {reinterpret_cast<void**>(&dout.win_state), out->win_state, nw},
+        {reinterpret_cast<void**>(&dout.win_sample_reads), out->win_sample_reads, 4 * nw * S},
+        {reinterpret_cast<void**>(&dout.win_sample_bases), out->win_sample_bases, 8 * nw * S},
+        {reinterpret_cast<void**>(&dout.n_selected), out->n_selected, 8}, {reinterpret_cast<void**>(&dout.sel_win_off), out->sel_win_off, 4 * (nw + 1)},
+        {reinterpret_cast<void**>(&dout.sel_off), out->sel_off, 8 * L}, {reinterpret_cast<void**>(&dout.sel_len), out->sel_len, 4 * L},
+        {reinterpret_cast<void**>(&dout.sel_sample), out->sel_sample, L}, {reinterpret_cast<void**>(&dout.sel_src), out->sel_src, 4 * L}};
+  };
+  if (host) {
+    struct Item { const void* src; size_t bytes; const void** dst; };
+    Item const items[6] = {{in->blob, static_cast<size_t>(in->blob_bytes), reinterpret_cast<const void**>(&din.blob)},
+                           {in->rec_off, 8 * n, reinterpret_cast<const void**>(&din.rec_off)},
+                           {in->rec_len, 4 * n, reinterpret_cast<const void**>(&din.rec_len)},
+                           {in->rec_win_off, 4 * (nw + 1), reinterpret_cast<const void**>(&din.rec_win_off)},
+                           {in->rec_sample, n, reinterpret_cast<const void**>(&din.rec_sample)},
+                           {sp->win_len, 4 * nw, reinterpret_cast<const void**>(&dsp.win_len)}};
+    for (int i = 0; i < 6; ++i) {
+      MA_HIP(ctx, ctx->sl_in[i].reserve(items[i].bytes + 16));
+      if (items[i].bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->sl_in[i].p, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+      *items[i].dst = ctx->sl_in[i].p;
+    }
+    std::vector<OutItem> const oi = out_items(n);
+    for (size_t i = 0; i < oi.size(); ++i) {
+      MA_HIP(ctx, ctx->sl_out[i].reserve(oi[i].bytes + 16));
+      *oi[i].dev = ctx->sl_out[i].p;
+    }
+  }
+  // (the members of `in` this call does not read stay out of the kernels' reach)
+  din.sample_index = din.sample_case = nullptr;
+  din.sample_rank = nullptr;
+  din.ref_map = nullptr;
+  din.win_chrom = nullptr;
+  din.win_start0 = nullptr;
+  u64 st[4] = {0, 0, 0, 0};
+  MA_TRY(launch_select(ctx, din, dsp, dout, st));
+  if (st[1] & 1u) {
+    ma_set_err(ctx, "ma_select_records_batch: rec_win_off does not rise from 0 to n_records");
+    return MA_ERR_ARG;
+  }
+  if (st[0] != ~0ull) {
+    ma_set_err(ctx, "ma_select_records_batch: record " + std::to_string(st[0]) +
+                        " does not fit its rec_len or the blob, or has no bases, no name or no such sample");
+    return MA_ERR_ARG;
+  }
+  if (host) {
+    std::vector<OutItem> const oi = out_items(st[2]);
+    for (size_t i = 0; i < oi.size(); ++i)
       if (oi[i].bytes) MA_HIP(ctx, hipMemcpyAsync(oi[i].user, *oi[i].dev, oi[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));
   }

@@ -62,6 +62,8 @@ def load_library(path=None):
         lib.ma_last_poa_export.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     if hasattr(lib, "ma_flatten_records_batch"):  # (likewise: a build of before the record flattening)
         lib.ma_flatten_records_batch.argtypes = [C.c_void_p] * 3
+    if hasattr(lib, "ma_select_records_batch"):  # (likewise: a build of before the record selection)
+        lib.ma_select_records_batch.argtypes = [C.c_void_p] * 4
     return lib
 
 
@@ -235,6 +237,39 @@ class Engine:
         rc = self.lib.ma_flatten_records_batch(self.h, C.byref(records_struct), C.byref(flat_struct))
         if rc != 0:
             e = EngineError(f"ma_flatten_records_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+
+    def select_records(self, rec_arrays, n_windows, n_records, win_len, max_sample_cov=1000.0, min_anchor_cov=5,
+                       skip_active_region=False):
+        """ma_select_records_batch: the candidates of every window (`rec_arrays`: blob, rec_off, rec_len, rec_win_off,
+        rec_sample and 'n_samples_in' or sample_rank for the sample count) -> dict of the capi.select_out_spec arrays, the four
+        sel_ arrays cut to n_selected.  Raises EngineError with .rc = the ma_error and .arrays = the arrays as the call left
+        them."""
+        rec = {k: np.ascontiguousarray(rec_arrays[k], dtype=capi.RECORDS_DTYPES[k]) for k in capi.SELECT_IN_KEYS}
+        n_samples = int(rec_arrays["n_samples_in"] if "n_samples_in" in rec_arrays else len(rec_arrays["sample_rank"]))
+        rec["win_len"] = np.ascontiguousarray(win_len, dtype=np.uint32)
+        out = self._alloc(capi.select_out_spec(n_windows, n_records, n_samples))
+        # (an empty array has no address worth passing: every member is required to be non-NULL)
+        held = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in list(rec.items()) + list(out.items())}
+        rs = capi.make_records_struct(dict(held, n_samples_in=n_samples), n_windows, n_records, blob_bytes=rec["blob"].size)
+        sp = capi.make_select_params(held["win_len"], max_sample_cov, min_anchor_cov, skip_active_region)
+        try:
+            self.select_records_device(rs, sp, capi.fill_struct(capi.SelectOut, held))
+        except EngineError as e:
+            e.arrays = out
+            raise
+        out["n_selected"] = held["n_selected"]
+        total = int(held["n_selected"][0])
+        for k in ("sel_off", "sel_len", "sel_sample", "sel_src"):
+            out[k] = out[k][:total]
+        return out
+
+    def select_records_device(self, records_struct, select_params, select_out):
+        """ma_select_records_batch on caller-made structs (either memory space)"""
+        rc = self.lib.ma_select_records_batch(self.h, C.byref(records_struct), C.byref(select_params), C.byref(select_out))
+        if rc != 0:
+            e = EngineError(f"ma_select_records_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
             e.rc = rc
             raise e
 

@@ -87,6 +87,37 @@ inline uint64_t HashQname(std::string_view q) {  // (the reference hashes with a
   for (char c : q) h = (h ^ static_cast<uint8_t>(c)) * 1099511628211ull;
   return h;
 }
+// the auxiliary fields of a BAM record, `b + p` on: only MD (type Z or H; the last one) and the presence of SA matter here
+inline void WalkAuxFields(const unsigned char* b, size_t block, size_t p, std::string_view* md, bool* has_md, bool* has_sa) {
+  while (p + 3 <= block) {
+    char const t0 = static_cast<char>(b[p]), t1 = static_cast<char>(b[p + 1]), ty = static_cast<char>(b[p + 2]);
+    p += 3;
+    size_t len = 0;
+    if (ty == 'Z' || ty == 'H') {
+      const void* const nul = std::memchr(b + p, 0, block - p);
+      if (!nul) break;  // unterminated string: nothing further can be trusted
+      len = static_cast<size_t>(static_cast<const unsigned char*>(nul) - (b + p)) + 1;
+      if (t0 == 'M' && t1 == 'D') {
+        *md = std::string_view(reinterpret_cast<const char*>(b + p), len - 1);
+        *has_md = true;
+      }
+      if (t0 == 'S' && t1 == 'A') *has_sa = true;
+    } else if (ty == 'A' || ty == 'c' || ty == 'C') len = 1;
+    else if (ty == 's' || ty == 'S') len = 2;
+    else if (ty == 'i' || ty == 'I' || ty == 'f') len = 4;
+    else if (ty == 'B') {
+      if (p + 5 > block) break;
+      char const sub = static_cast<char>(b[p]);
+      int32_t cnt;
+      std::memcpy(&cnt, b + p + 1, 4);
+      if (cnt < 0) break;
+      size_t const es = (sub == 'c' || sub == 'C') ? 1 : ((sub == 's' || sub == 'S') ? 2 : 4);
+      len = 5 + es * static_cast<size_t>(cnt);
+    } else break;
+    if (len > block - p) break;
+    p += len;
+  }
+}
 struct SamRecord {
   std::string qname;
   uint16_t flag = 0;
@@ -109,7 +140,11 @@ struct SamRecord {
   // raw_blob, the window into the batch's).  qname, cigar, seq, seq4
   // and qual stay empty; what the filters, the coverage cap and IsActiveRegion need beyond the fixed fields is kept as scalars
   // (the name's hash, the reference span) or read from the bytes (CIGAR words, qualities).  `packed` is set: SeqLen() is l_seq4
+  // With keep_tags (--device-select) `raw` is the record's WHOLE block, auxiliary fields included; raw_core is where they begin
+  // and nothing of them is decoded when the record is made: `md` stays empty, Md() finds the string in the bytes when asked
+  // (CheckAlignment on the host route of a window the device handed back).
   std::vector<uint8_t> raw;
+  uint32_t raw_core = 0;  // bytes of the core part
   bool is_raw = false;
   uint64_t raw_qh = 0;    // HashQname of the name
   int64_t raw_span = 1;   // RefSpan()
@@ -122,11 +157,16 @@ struct SamRecord {
     std::memcpy(&v, raw.data() + 32 + raw[8] + 4 * i, 4);
     return {(v & 15u) < 9 ? kOps[v & 15u] : '?', v >> 4};
   }
-  const uint8_t* QualData() const { return is_raw ? raw.data() + raw.size() - l_seq4 : qual.data(); }
+  const uint8_t* QualData() const { return is_raw ? raw.data() + raw_core - l_seq4 : qual.data(); }
   size_t QualSize() const { return is_raw ? l_seq4 : qual.size(); }
   std::vector<uint8_t> qual;
   std::string md;
   bool has_md = false, has_sa = false;
+  // the MD string: decoded (`md`), or found in a whole-block raw record's auxiliary fields; false: the record has none.
+  // On a keep_tags record `md`, `has_md` and `has_sa` are NOT filled (nothing was walked): read MD through Md() only -- it walks
+  // the fields anew on every call, once per record on the host route.  has_sa has one reader, the mate collection of
+  // --extract-pairs (ReadCollector::CollectRegion), which the driver refuses together with raw records
+  inline bool Md(std::string_view* out) const;
   bool IsQcFail() const { return flag & 0x200; }
   bool IsDuplicate() const { return flag & 0x400; }
   bool IsUnmapped() const { return flag & 0x4; }
@@ -155,6 +195,16 @@ struct SamRecord {
   int32_t InsertSize32() const { return static_cast<int32_t>(std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, tlen))); }
   int32_t Start32() const { return static_cast<int32_t>(std::max<int64_t>(0, std::min<int64_t>(INT32_MAX, pos0))); }
 };
+
+inline bool SamRecord::Md(std::string_view* out) const {
+  if (is_raw && raw.size() > raw_core) {
+    bool found = false, sa = false;
+    WalkAuxFields(raw.data(), raw.size(), raw_core, out, &found, &sa);
+    return found;
+  }
+  *out = md;
+  return has_md;
+}
 
 inline std::vector<CigarUnit> ParseCigar(std::string_view s) {
   std::vector<CigarUnit> out;
@@ -387,7 +437,7 @@ class AlignmentSource {
             done = true;  // coordinate-sorted: nothing further in this chunk (or any later one) overlaps
             continue;
           }
-          SamRecord rec = DecodeBamRecord(buf.data(), buf.size(), ref_map_, keep_packed_, keep_raw_);
+          SamRecord rec = DecodeBamRecord(buf.data(), buf.size(), ref_map_, keep_packed_, keep_raw_, keep_tags_);
           if (rec.pos0 + rec.RefSpan() > s0) fn(rec);
         }
         if (done) break;
@@ -455,8 +505,9 @@ class AlignmentSource {
   // one BAM alignment record (SAM specification 4.2; `b` points behind its block_size field)
   // keep_packed: the sequence stays as the file has it (SamRecord::seq4: 4-bit codes, high nibble first), `seq` stays empty
   // keep_raw: SamRecord's raw mode -- the core bytes in one vector, no name string, no CIGAR vector, no decoded sequence
+  // keep_tags (with keep_raw): the whole block is kept and its auxiliary fields are not walked (SamRecord::Md does, on demand)
   static SamRecord DecodeBamRecord(const unsigned char* b, size_t block, std::vector<int> const& ref_map, bool keep_packed = false,
-                                   bool keep_raw = false) {
+                                   bool keep_raw = false, bool keep_tags = false) {
     static const char* kSeq = "=ACMGRSVTWYHKDBN";
     static const char* kOps = "MIDNSHP=X";
     auto rd32 = [&](size_t at) { int32_t v; std::memcpy(&v, b + at, 4); return v; };
@@ -482,7 +533,8 @@ class AlignmentSource {
       throw std::runtime_error("corrupt BAM record: its fields do not fit its block");
     size_t const core = 32 + static_cast<size_t>(l_read_name) + 4u * static_cast<size_t>(n_cigar) + (static_cast<size_t>(l_seq) + 1) / 2 + static_cast<size_t>(l_seq);
     if (keep_raw) {  // the core bytes as they are, and the two scalars the collector needs of them
-      r.raw.assign(b, b + core);
+      r.raw.assign(b, b + (keep_tags ? block : core));
+      r.raw_core = static_cast<uint32_t>(core);
       r.is_raw = r.packed = true;
       r.l_seq4 = static_cast<uint32_t>(l_seq);
       r.raw_qh = HashQname(std::string_view(reinterpret_cast<const char*>(b + p), l_read_name ? l_read_name - 1u : 0u));
@@ -512,40 +564,17 @@ class AlignmentSource {
       p += static_cast<size_t>(l_seq + 1) / 2;
       r.qual.assign(b + p, b + p + l_seq);
     }
-    p = core;  // the auxiliary fields follow the core in either mode
-    while (p + 3 <= block) {  // auxiliary fields: only MD:Z and the presence of SA matter here
-      char const t0 = static_cast<char>(b[p]), t1 = static_cast<char>(b[p + 1]), ty = static_cast<char>(b[p + 2]);
-      p += 3;
-      size_t len = 0;
-      if (ty == 'Z' || ty == 'H') {
-        const void* const nul = std::memchr(b + p, 0, block - p);
-        if (!nul) break;  // unterminated string: nothing further can be trusted
-        len = static_cast<size_t>(static_cast<const unsigned char*>(nul) - (b + p)) + 1;
-        if (t0 == 'M' && t1 == 'D') {
-          r.md.assign(reinterpret_cast<const char*>(b + p), len - 1);
-          r.has_md = true;
-        }
-        if (t0 == 'S' && t1 == 'A') r.has_sa = true;
-      } else if (ty == 'A' || ty == 'c' || ty == 'C') len = 1;
-      else if (ty == 's' || ty == 'S') len = 2;
-      else if (ty == 'i' || ty == 'I' || ty == 'f') len = 4;
-      else if (ty == 'B') {
-        if (p + 5 > block) break;
-        char const sub = static_cast<char>(b[p]);
-        int32_t const cnt = rd32(p + 1);
-        if (cnt < 0) break;
-        size_t const es = (sub == 'c' || sub == 'C') ? 1 : ((sub == 's' || sub == 'S') ? 2 : 4);
-        len = 5 + es * static_cast<size_t>(cnt);
-      } else break;
-      if (len > block - p) break;
-      p += len;
-    }
+    if (keep_raw && keep_tags) return r;
+    std::string_view md_view;  // the auxiliary fields follow the core in either mode
+    WalkAuxFields(b, block, core, &md_view, &r.has_md, &r.has_sa);
+    if (r.has_md) r.md.assign(md_view);
     return r;
   }
 
 #ifdef LANCET2_AMD_WITH_ZLIB
   // BAM: BGZF blocks are gzip members; the payload is the BAM record stream of the SAM specification, section 4.2
-  static AlignmentSource LoadBam(const std::string& path, Reference const& ref, bool keep_packed = false, bool keep_raw = false) {
+  static AlignmentSource LoadBam(const std::string& path, Reference const& ref, bool keep_packed = false, bool keep_raw = false,
+                                 bool keep_tags = false) {
     std::ifstream in(path, std::ios::binary);
     if (!in) throw std::runtime_error("cannot open alignments " + path);
     std::vector<unsigned char> comp((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
@@ -589,7 +618,7 @@ class AlignmentSource {
       size_t const b = at + 4;
       at = b + static_cast<size_t>(block);
       if (at > raw.size()) break;
-      src.recs.push_back(DecodeBamRecord(raw.data() + b, static_cast<size_t>(block), ref_map, keep_packed, keep_raw));
+      src.recs.push_back(DecodeBamRecord(raw.data() + b, static_cast<size_t>(block), ref_map, keep_packed, keep_raw, keep_tags));
     }
     src.ref_map_ = ref_map;
     src.Finish(ref.chroms.size());
@@ -597,10 +626,11 @@ class AlignmentSource {
   }
   // BAM + .bai: header only; records are fetched per region (ForRegion)
   static AlignmentSource OpenIndexedBam(const std::string& path, const std::string& bai_path, Reference const& ref, bool keep_packed = false,
-                                        bool keep_raw = false) {
+                                        bool keep_raw = false, bool keep_tags = false) {
     AlignmentSource src;
     src.keep_packed_ = keep_packed;
     src.keep_raw_ = keep_raw;
+    src.keep_tags_ = keep_tags;
     src.index_ = std::make_shared<BamIndex>(BamIndex::Load(bai_path));
     src.path_ = path;
     src.bgzf_ = std::make_shared<BgzfFile>(path);
@@ -635,6 +665,7 @@ class AlignmentSource {
     c.chrom_rid_ = chrom_rid_;
     c.keep_packed_ = keep_packed_;
     c.keep_raw_ = keep_raw_;
+    c.keep_tags_ = keep_tags_;
     return c;
   }
   bool indexed() const { return bgzf_ != nullptr; }
@@ -652,6 +683,7 @@ class AlignmentSource {
   std::vector<int> ref_map_;    // BAM reference id -> chromosome of the FASTA (-1: not in it)
   std::vector<int> chrom_rid_;  // and back
   bool keep_raw_ = false;       // --raw-records: SamRecord's raw mode
+  bool keep_tags_ = false;      // ... with the whole block kept (the candidates of ma_select_records_batch)
   bool keep_packed_ = false;    // --packed-reads: records keep their sequence bytes undecoded (for ReadCollector::Params::packed_reads)
 #endif
 };
@@ -876,7 +908,8 @@ struct MutationAccumulator {
   }
   bool CheckAlignment(SamRecord const& a) {
     if (a.IsQcFail() || a.IsDuplicate() || a.IsUnmapped() || a.mapq == 0) return false;
-    if (a.has_md && ParseMd(a.md, a.QualData(), a.QualSize(), a.pos0, &mismatches)) return true;
+    std::string_view md;
+    if (a.Md(&md) && ParseMd(md, a.QualData(), a.QualSize(), a.pos0, &mismatches)) return true;
     uint32_t gpos = static_cast<uint32_t>(a.pos0);
     size_t const n_ops = a.NumCigar();  // (a raw-mode record: the CIGAR words of its bytes)
     for (size_t k = 0; k < n_ops; ++k) {
@@ -1000,6 +1033,11 @@ class ReadCollector {
   // core bytes back to back in arrival order (FlatBatch::raw_blob: copied from the records) with their lengths and samples.  The sources must
   // be in raw mode (SamRecord::is_raw); returns false otherwise, and when the options need the general path (extract_pairs).
   bool CollectRaw(Window const& w, std::string_view ref_seq, struct FlatBatch* out);
+  // The window's CANDIDATES for ma_select_records_batch (include/microasm.h): every record ForRegion visits, sample after
+  // sample in arrival order, unfiltered, its whole block (the sources keep their tags: keep_tags) -- nothing is looked at here
+  // but the lengths.  `out` is a raw_mode batch with cand_mode set; its read_off counts the candidates' bases, an upper bound
+  // of what the selected ones hold.  Returns false when the sources are not in raw mode.
+  bool CollectCandidates(Window const& w, std::string_view ref_seq, struct FlatBatch* out);
   struct Kept {
     const SamRecord* rec;
     uint64_t qh;
@@ -1081,6 +1119,17 @@ struct FlatBatch {
   // goes to the chained call as a packed one with 8-bit qualities (`packed_view`, `packed`, `meta`).  Built by CollectRaw +
   // PlaceHeader / CopyPlaced / SizeForPlaced only, sealed by SealRaw().
   bool raw_mode = false;
+  // cand_mode (beside raw_mode; ReadCollector::CollectCandidates): the records are every window's CANDIDATES, the input of
+  // ma_select_records_batch.  SealCandidates() makes the views of that call (`records`, `sel_params`, `sel_out`); after it ran,
+  // UseSelected() points `records` and the batch views at the selected lists, so that ma_flatten_records_batch and the chained
+  // call take the batch as they take a CollectRaw one, and fills sample_cov from the call's sums.
+  bool cand_mode = false;
+  std::vector<uint8_t> rec_keep, win_state, sel_sample;
+  std::vector<uint32_t> win_len, win_sample_reads, sel_win_off, sel_len, sel_src;
+  std::vector<uint64_t> win_sample_bases, sel_off;
+  uint64_t n_selected = 0;
+  ma_select_params_t sel_params{};
+  ma_select_out_t sel_out{};
   ByteVec raw_blob;
   std::vector<uint64_t> rec_off;
   std::vector<uint32_t> rec_len;
@@ -1244,6 +1293,9 @@ struct FlatBatch {
     placed_ref_ = placed_reads_ = placed_raw_ = 0;
     placed_bases_ = 0;
     raw_blob.clear(); rec_off.clear(); rec_len.clear(); rec_sample.clear(); win_chrom.clear(); win_start0.clear();
+    n_selected = 0;
+    sel_params = ma_select_params_t{};
+    sel_out = ma_select_out_t{};
     records = ma_records_t{};
     flat_out = ma_flat_out_t{};
     n_bases_out = 0;
@@ -1327,6 +1379,33 @@ struct FlatBatch {
     meta.read_isize = read_isize.data(); meta.read_start = read_start.data();
   }
   std::vector<uint32_t> read_src;  // raw_mode: which record each read is (ma_flat_out_t::read_src)
+  void SealCandidates(RawTables const& t, double max_sample_cov, uint32_t min_anchor_cov, bool skip_active_region) {
+    SealRaw(t);
+    size_t const nr = rec_len.size(), nw = windows.size(), ns = t.index.size();
+    win_len.resize(nw);
+    for (size_t w = 0; w < nw; ++w) win_len[w] = static_cast<uint32_t>(windows[w].Length());
+    rec_keep.resize(std::max<size_t>(nr, 1)); win_state.resize(std::max<size_t>(nw, 1));
+    win_sample_reads.resize(std::max<size_t>(nw * ns, 1)); win_sample_bases.resize(std::max<size_t>(nw * ns, 1));
+    sel_win_off.resize(nw + 1);
+    sel_off.resize(std::max<size_t>(nr, 1)); sel_len.resize(std::max<size_t>(nr, 1)); sel_sample.resize(std::max<size_t>(nr, 1));
+    sel_src.resize(std::max<size_t>(nr, 1));
+    sel_params = ma_select_params_t{max_sample_cov, min_anchor_cov, skip_active_region ? 1 : 0, win_len.data()};
+    sel_out = ma_select_out_t{rec_keep.data(), win_state.data(), win_sample_reads.data(), win_sample_bases.data(), &n_selected,
+                              sel_win_off.data(), sel_off.data(), sel_len.data(), sel_sample.data(), sel_src.data()};
+  }
+  void UseSelected() {
+    size_t const nw = windows.size(), ns = static_cast<size_t>(records.n_samples_in);
+    records.n_records = static_cast<int64_t>(n_selected);
+    records.rec_off = sel_off.data(); records.rec_len = sel_len.data(); records.rec_win_off = sel_win_off.data();
+    records.rec_sample = sel_sample.data();
+    view.n_reads = static_cast<int64_t>(n_selected);
+    view.read_win_off = sel_win_off.data();
+    packed_view = view;
+    for (size_t w = 0; w < nw; ++w) {
+      sample_cov[w].assign(ns, 0.0);
+      for (size_t s = 0; s < ns; ++s) sample_cov[w][s] = static_cast<double>(win_sample_bases[w * ns + s]) / static_cast<double>(windows[w].Length());
+    }
+  }
   // --packed-reads (include/microasm.h: ma_packed_reads_t), after Seal(): the batch's quality dictionary -- 4-bit codes into
   // the distinct Phred values in ascending order when there are at most 16 of them, the Phred bytes as they are (qual_bits =
   // 8) otherwise -- and, unless the batch was built in packed_mode (bases4 is in place then), the read bases packed from
@@ -1576,6 +1655,61 @@ inline bool ReadCollector::CollectRaw(Window const& w, std::string_view ref_seq,
   fb.read_off.push_back(fb.read_off.back() + total_bases);  // (one entry per WINDOW here: what PlaceHeader adds up)
   fb.read_win_off.push_back(static_cast<uint32_t>(fb.rec_len.size()));
   return true;
+}
+
+inline bool ReadCollector::CollectCandidates(Window const& w, std::string_view ref_seq, FlatBatch* out) {
+  FlatBatch& fb = *out;
+  fb.raw_mode = fb.cand_mode = true;
+  fb.windows.push_back(w);
+  fb.sample_cov.emplace_back(samples_.size(), 0.0);  // (known once the device has counted: FlatBatch::UseSelected)
+  fb.ref_bases.insert(fb.ref_bases.end(), ref_seq.begin(), ref_seq.end());
+  fb.ref_off.push_back(static_cast<uint32_t>(fb.ref_bases.size()));
+  uint64_t bases = 0;
+  bool all_raw = true;
+  // an in-memory source's records stay where they are: they are listed first and copied once the window's size is known; an
+  // indexed source hands out temporaries, which are appended as they come
+  std::vector<std::pair<const SamRecord*, uint8_t>> listed;
+  size_t bytes = fb.raw_blob.size();
+  for (size_t si = 0; si < samples_.size(); ++si) {
+#ifdef LANCET2_AMD_WITH_ZLIB
+    bool const own = samples_[si].source->indexed();
+#else
+    bool const own = false;
+#endif
+    samples_[si].source->ForRegion(w.chrom, static_cast<int64_t>(w.start1), static_cast<int64_t>(w.end1), [&](SamRecord const& a) {
+      if (!a.is_raw) {
+        all_raw = false;
+        return;
+      }
+      bases += a.SeqLen();
+      if (!own) {
+        listed.emplace_back(&a, static_cast<uint8_t>(si));
+        bytes += a.raw.size();
+        return;
+      }
+      fb.rec_off.push_back(fb.raw_blob.size());
+      fb.rec_len.push_back(static_cast<uint32_t>(a.raw.size()));
+      fb.rec_sample.push_back(static_cast<uint8_t>(si));
+      fb.raw_blob.insert(fb.raw_blob.end(), a.raw.begin(), a.raw.end());
+    });
+    if (own || listed.empty()) continue;
+    size_t at = fb.raw_blob.size();
+    size_t const r0 = fb.rec_len.size();
+    fb.raw_blob.resize(bytes);
+    fb.rec_off.resize(r0 + listed.size()); fb.rec_len.resize(r0 + listed.size()); fb.rec_sample.resize(r0 + listed.size());
+    for (size_t i = 0; i < listed.size(); ++i) {
+      std::vector<uint8_t> const& raw = listed[i].first->raw;
+      std::memcpy(fb.raw_blob.data() + at, raw.data(), raw.size());
+      fb.rec_off[r0 + i] = at;
+      fb.rec_len[r0 + i] = static_cast<uint32_t>(raw.size());
+      fb.rec_sample[r0 + i] = listed[i].second;
+      at += raw.size();
+    }
+    listed.clear();
+  }
+  fb.read_off.push_back(fb.read_off.back() + bases);  // (one entry per WINDOW here: what PlaceHeader adds up)
+  fb.read_win_off.push_back(static_cast<uint32_t>(fb.rec_len.size()));
+  return all_raw;
 }
 
 // the tables of a collector's samples (its sorted order: rec_sample is a position in it)

@@ -4,7 +4,10 @@ index: the files are read whole).  Builds examples/pipeline_driver.cpp -O3 -marc
 --parent-src DIR (a checkout of another commit: DIR/examples, DIR/include, DIR/lancet2_amd/host), that commit's driver too;
 runs `--extract-only --no-active-region` with 1 and N collector threads, three times each, and prints windows/s handed over and
 cpu-seconds of collection per window (median and the three runs).
-usage: python tools/extract_cost.py [--parent-src DIR] [--threads N] [--genome-len L]"""
+With --active-region the reads carry a planted SNV every 700 bases (sequence bytes and MD strings say so), the runs leave
+active-region detection ON, and a third leg runs `--raw-records --device-select`: the collector lists every candidate and looks
+at none -- the filters, the detection and the coverage gates are the engine's (ma_select_records_batch).
+usage: python tools/extract_cost.py [--parent-src DIR] [--threads N] [--genome-len L] [--active-region]"""
 import argparse
 import os
 import re
@@ -20,7 +23,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def write_bam(path, genome, name, depth, rng):
+def write_bam(path, genome, name, depth, rng, snv_every=0):
     """coordinate-sorted BAM of genome_len * depth / 300 pairs; returns the number of records"""
     glen = len(genome)
     code = np.zeros(256, np.uint8)
@@ -44,6 +47,16 @@ def write_bam(path, genome, name, depth, rng):
     for pos0, i, flag, mate in recs:
         qn = b"%c%d\0" % (name[0].encode(), i)
         seq = (even if pos0 % 2 == 0 else odd)[pos0 // 2:pos0 // 2 + 75]
+        tag = b"MDZ150\0"
+        site = -(-pos0 // snv_every) * snv_every if snv_every else glen
+        if site < pos0 + 150:  # the planted SNV: the next base code in the read, the reference's letter in the MD string
+            at = site - pos0
+            was = int(c[site])
+            now = {1: 2, 2: 4, 4: 8, 8: 1}[was]
+            seq = bytearray(seq)
+            seq[at // 2] = (seq[at // 2] & (0x0F if at % 2 == 0 else 0xF0)) | (now << (4 if at % 2 == 0 else 0))
+            seq = bytes(seq)
+            tag = b"MDZ%d%c%d\0" % (at, genome[site], 149 - at)
         body = struct.pack("<iiBBHHHiiii", 0, pos0, len(qn), 60, 4680, 1, flag, 150, 0, mate, mate - pos0) + qn + cigar + seq + qual + tag
         out += struct.pack("<i", len(body)) + body
     with open(path, "wb") as fh:
@@ -63,10 +76,10 @@ def build_driver(src_root, exe):
                            "-DLANCET2_AMD_WITH_ZLIB", "-lz", "-lpthread", "-o", exe])
 
 
-def run(exe, d, mode, nthreads):
+def run(exe, d, mode, nthreads, active_region=False):
     r = subprocess.run([exe, "--reference", os.path.join(d, "ref.fa"), "--normal", os.path.join(d, "normal.bam"), "--tumor",
-                        os.path.join(d, "tumor.bam"), "--no-active-region", "--extract-only", "--extract-threads", str(nthreads), mode],
-                       capture_output=True, text=True)
+                        os.path.join(d, "tumor.bam"), "--extract-only", "--extract-threads", str(nthreads)] +
+                       ([] if active_region else ["--no-active-region"]) + mode.split(), capture_output=True, text=True)
     m = re.search(r"extract ([0-9.]+) s busy \(([0-9.]+) windows/s tiled, ([0-9.]+) shipped/s\) with (\d+) collector thread\(s\), ([0-9.]+) cpu-s of collection", r.stderr)
     if r.returncode != 0 or not m:
         raise RuntimeError(f"{exe} {mode}: " + r.stderr[-300:])
@@ -79,25 +92,31 @@ def main():
     ap.add_argument("--parent-src")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--genome-len", type=int, default=2_400_000)
+    ap.add_argument("--active-region", action="store_true")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="ma_extract_") as d:
         rng = np.random.default_rng(0x5EED)
         genome = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, args.genome_len)]
         with open(os.path.join(d, "ref.fa"), "w") as f:
             f.write(">chr1\n" + bytes(genome).decode() + "\n")
-        nrec = sum(write_bam(os.path.join(d, name + ".bam"), genome, name, depth, rng) for name, depth in (("normal", 30), ("tumor", 60)))
+        nrec = sum(write_bam(os.path.join(d, name + ".bam"), genome, name, depth, rng, 700 if args.active_region else 0)
+                   for name, depth in (("normal", 30), ("tumor", 60)))
         legs = []
         if args.parent_src:
             build_driver(args.parent_src, os.path.join(d, "driver_parent"))
-            legs.append(("parent --packed-reads", os.path.join(d, "driver_parent"), "--packed-reads"))
+            legs.append(("parent --raw-records" if args.active_region else "parent --packed-reads", os.path.join(d, "driver_parent"),
+                         "--raw-records" if args.active_region else "--packed-reads"))
         build_driver(REPO, os.path.join(d, "driver"))
         legs += [("this --packed-reads", os.path.join(d, "driver"), "--packed-reads"), ("this --raw-records", os.path.join(d, "driver"), "--raw-records")]
-        print(f"{args.genome_len} bases, {nrec} records, BAM read whole; -O3 -march=native; three runs each, in turn")
+        if args.active_region:
+            legs.append(("this --raw-records --device-select", os.path.join(d, "driver"), "--raw-records --device-select"))
+        print(f"{args.genome_len} bases, {nrec} records, BAM read whole; -O3 -march=native; three runs each, in turn; active-region detection "
+              f"{'on, an SNV every 700 bases' if args.active_region else 'off'}")
         res = {}
         for rep in range(3):  # the legs alternate: a drift of the machine hits all of them
             for nthreads in (1, args.threads):
                 for label, exe, mode in legs:
-                    res.setdefault((label, nthreads), []).append(run(exe, d, mode, nthreads))
+                    res.setdefault((label, nthreads), []).append(run(exe, d, mode, nthreads, args.active_region))
         for (label, nthreads), runs in res.items():
             wps, us = [r[0] for r in runs], [r[1] for r in runs]
             print(f"{label}, {nthreads} collector thread(s): {statistics.median(wps):.0f} windows/s (runs {[round(x) for x in wps]}), "
