@@ -30,6 +30,9 @@
  *                             core::ActiveRegionDetector (core/active_region_detector.cpp:85-232) and the anchor-coverage gate
  *                             (core/variant_builder.cpp:214-224) on every candidate record of a window: which records go on,
  *                             as the lists ma_flatten_records_batch takes
+ *   ma_inflate_blocks_batch <- htslib's BGZF reader under hts::Extractor (hts/extractor.cpp): compressed BGZF blocks to their
+ *                             payloads, CRC checked, on the device; ma_index_records_batch <- its record iteration: where the
+ *                             alignment records of the inflated bytes are, with refID, pos and reference span of each
  *
  * Conventions: plain pointers and sizes only; all buffers are caller owned, struct-of-arrays;
  * every function returns 0 on success and a negative ma_error otherwise and never throws.
@@ -741,6 +744,112 @@ typedef struct ma_select_out {  /* every member required */
   uint64_t* sel_off; uint32_t* sel_len; uint8_t* sel_sample; uint32_t* sel_src;  /* [n_records] each, *n_selected written */
 } ma_select_out_t;
 int ma_select_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_select_params_t* sp, const ma_select_out_t* out);
+
+/* ---- BGZF blocks inflated on the device ------------------------------------------------------------------------------------------ */
+/* What the host shell's BgzfFile::Load does a block at a time with zlib, for a list of blocks at once and with the CRC-32 that
+ * Load leaves out: the compressed members of a BAM file go up, their payloads stay on the device as one byte array, which is the
+ * `blob` of ma_records_t.  A BGZF block is a gzip member (RFC 1952) with an extra subfield that tells its size (SAM specification
+ * 4.1); its data is one DEFLATE stream (RFC 1951).
+ * INPUT.  Block b is the blk_len[b] bytes of cblob from blk_off[b], which must lie inside cblob: the bytes AVAILABLE for the
+ * member, the member itself may be shorter.  Any alignment, any order, gaps, overlaps and repeats are allowed.
+ * HEADER RULES (BgzfFile::Load's).  Bytes 0 .. 3 are 1f 8b 08 and a FLG with bit 2 set; XLEN is the 16-bit value at byte 10; the
+ * extra field, bytes [12, 12 + XLEN), is a chain of subfields SI1 SI2 SLEN(16 bits) data[SLEN], walked while 4 bytes are left; a
+ * subfield that passes the end of the extra field breaks the rule; the last subfield 'B' 'C' with SLEN 2 holds BSIZE, the
+ * member's size less one (none: the rule is broken); 12 + XLEN + 8 <= BSIZE + 1 <= blk_len.  blk_len < 20 breaks the rule too.
+ * The DEFLATE data are bytes [12 + XLEN, BSIZE + 1 - 8), the trailer is CRC32 then ISIZE, 32 bits each, little endian.
+ * BLOCK STATE (blk_state, one byte per block; 0: good, otherwise exactly one of)
+ *   MA_Z_HEADER  a header rule is broken                     } the block contributes 0 bytes: blk_raw_off[b + 1] == blk_raw_off[b]
+ *   MA_Z_ISIZE   ISIZE > 65536                               }
+ *   MA_Z_DATA    the DEFLATE stream is invalid, needs a bit from behind its data bytes, or would write more than ISIZE bytes.
+ *                Invalid is what zlib's inflate rejects: block type 3; a stored block with LEN != ~NLEN; more than 286
+ *                literal/length or more than 30 distance code lengths; an over-subscribed code-length, literal/length or
+ *                distance code; an incomplete one, except a code with no lengths at all (using it is invalid) and, for
+ *                literal/length and distance codes, a single code of length 1 (the other bit pattern is invalid); repeat code 16
+ *                as the first code length, a repeat that passes the count of lengths; no code for symbol 256; a bit pattern
+ *                without a code; literal/length symbols 286, 287 and distance symbols 30, 31 of the fixed code; a distance
+ *                greater than the bytes this block has written so far (there is no dictionary and no window across blocks)
+ *   MA_Z_SHORT   the last DEFLATE block (BFINAL) ended with fewer than ISIZE bytes written
+ *   MA_Z_CRC     ISIZE bytes were written and their CRC-32 is not the trailer's
+ * A member with ISIZE 0 is decoded and checked like any other (the 28-byte end-of-file member is good).  Data bytes left over
+ * between the end of the last DEFLATE block and the trailer are not an error (zlib's Z_FINISH accepts them, and so does Load).
+ * OUTPUT.  blk_raw_off[0] = 0, blk_raw_off[b + 1] = blk_raw_off[b] + (ISIZE of block b, 0 for MA_Z_HEADER and MA_Z_ISIZE);
+ * *n_raw = blk_raw_off[n_blocks]; raw[blk_raw_off[b] .. blk_raw_off[b + 1]) is the payload of a good block -- list order, no
+ * gaps, so a record that straddles two blocks of the file is contiguous in raw.  A flagged block never fails the call; the
+ * bytes of its own range are undefined, nothing outside of it is written.  *n_flagged counts the blocks with a state != 0.
+ * ERRORS, never silent; after any of them no output is defined, and none but *n_raw in the second case is written:
+ *   MA_ERR_ARG   blk_off[b] + blk_len[b] > cblob_bytes: ma_last_error names the first such block
+ *   MA_ERR_ARG   *n_raw > raw_cap: *n_raw holds the need, re-submit with that capacity
+ *   MA_ERR_ARG   n_blocks < 0, a NULL member of `in` or `out` (cblob, blk_off, blk_len and raw too, even where empty)
+ * Both memory spaces like ma_flatten_records_batch; one 32-byte status block is read back per call, with MA_MEM_DEVICE nothing
+ * else crosses the link.  No kernel reads outside [cblob, cblob + cblob_bytes) -- the bit reader's loads are byte loads in front
+ * of the member's trailer -- or writes outside the output arrays, whatever a block claims.  Three kernels of its own
+ * (inflate.hip), reported by ma_last_kernel_times as k_inf_header, k_inf_scan, k_inf_decode (the last one only with
+ * n_blocks > 0); no other call runs them and this call runs no other kernel. */
+#define MA_Z_HEADER 1
+#define MA_Z_ISIZE 2
+#define MA_Z_DATA 4
+#define MA_Z_SHORT 8
+#define MA_Z_CRC 16
+typedef struct ma_bgzf {
+  int64_t n_blocks;
+  const uint8_t* cblob;         /* BGZF members as they are in the file */
+  uint64_t cblob_bytes;
+  const uint64_t* blk_off;      /* [n_blocks] offset in cblob of the member's first byte (0x1f) */
+  const uint32_t* blk_len;      /* [n_blocks] bytes available from there (>= BSIZE + 1 for a good block) */
+} ma_bgzf_t;
+typedef struct ma_inflate_out { /* every member required */
+  uint64_t raw_cap;             /* caller's capacity of raw in bytes */
+  uint8_t* raw;
+  uint64_t* blk_raw_off;        /* [n_blocks + 1] */
+  uint8_t* blk_state;           /* [n_blocks] MA_Z_* */
+  uint64_t* n_raw;              /* [1] */
+  uint64_t* n_flagged;          /* [1] */
+} ma_inflate_out_t;
+int ma_inflate_blocks_batch(ma_ctx_t* ctx, const ma_bgzf_t* in, const ma_inflate_out_t* out);
+
+/* ---- the alignment records in inflated bytes ---------------------------------------------------------------------------------------- */
+/* Finds the BAM alignment records (SAM specification 4.2) of byte ranges of `raw` -- the output of ma_inflate_blocks_batch, or
+ * any inflated BAM bytes -- so that a host can assign records to windows from 12 bytes per record without seeing the bytes.
+ * A STREAM s is walked from str_begin[s], the offset of a record's block_size field: with p the place of that field, the
+ * walk goes on while p < str_end[s] (a record that STARTS before str_end belongs to the stream, as with a BAI chunk's end);
+ * the record is the block_size bytes from p + 4, the next one's field is at p + 4 + block_size.  The walk ends, with
+ * MA_X_BAD_RECORD in str_state[s], at a record
+ *   - whose block_size field or whose block_size bytes pass raw_bytes (p + 4 + block_size > raw_bytes),
+ *   - with block_size < 32,
+ *   - whose core 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq, l_seq read as unsigned, exceeds block_size;
+ * the records in front of it are kept, it is not listed itself.  Streams may overlap; a record in two streams is listed twice.
+ * OUTPUT.  str_rec_off (exclusive sums of the streams' record counts, n_streams + 1 values), *n_found = the last of them,
+ * str_state (0 or MA_X_BAD_RECORD), and per record in stream order, then file order: rec_off (the offset in raw of refID, that
+ * is p + 4) and rec_len (block_size) -- exactly what ma_records_t takes with blob = raw -- and rec_ref (refID), rec_pos (pos,
+ * 0-based, as stored) and rec_span: the sum of the lengths of the CIGAR operations M, D, N, = and X (codes 0, 2, 3, 7, 8)
+ * modulo 2^32.  A CIGAR carried in a CG tag is not looked at (as in ma_flatten_records_batch).
+ * ERRORS, never silent; after any of them no output is defined, and none but *n_found in the second case is written:
+ *   MA_ERR_ARG   str_begin[s] > str_end[s] or str_end[s] > raw_bytes: ma_last_error names the first such stream
+ *   MA_ERR_ARG   *n_found > rec_cap: *n_found holds the need, re-submit with that capacity
+ *   MA_ERR_ARG   n_streams < 0, a NULL member of `in` or `out`
+ * Both memory spaces; one 32-byte status block is read back per call.  No kernel reads outside [raw, raw + raw_bytes).  Four
+ * kernels of its own (inflate.hip): k_idx_count, k_idx_scan, k_idx_fill, k_idx_fields (the first and third only with
+ * n_streams > 0, the last only with records found); no other call runs them and this call runs no other kernel. */
+#define MA_X_BAD_RECORD 1
+typedef struct ma_record_streams {
+  const uint8_t* raw;
+  uint64_t raw_bytes;
+  int64_t n_streams;
+  const uint64_t* str_begin;    /* [n_streams] offset in raw of the first record's block_size field */
+  const uint64_t* str_end;      /* [n_streams] */
+} ma_record_streams_t;
+typedef struct ma_index_out {   /* every member required */
+  uint64_t rec_cap;             /* caller's capacity of the five rec_ arrays in records */
+  uint64_t* n_found;            /* [1] */
+  uint64_t* str_rec_off;        /* [n_streams + 1] */
+  uint8_t* str_state;           /* [n_streams] MA_X_* */
+  uint64_t* rec_off;            /* [rec_cap], *n_found written: as ma_records_t takes it */
+  uint32_t* rec_len;
+  int32_t* rec_ref;
+  int32_t* rec_pos;
+  uint32_t* rec_span;
+} ma_index_out_t;
+int ma_index_records_batch(ma_ctx_t* ctx, const ma_record_streams_t* in, const ma_index_out_t* out);
 
 /* Work counters accumulated over the same region as ma_last_kernel_times (reset by ma_timing_control):
  *   out[0] read x haplotype pairs seen by ma_genotype_batch      out[1] pairs that needed the DP

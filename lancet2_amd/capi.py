@@ -373,6 +373,77 @@ def make_select_params(win_len, max_sample_cov=1000.0, min_anchor_cov=5, skip_ac
     return s
 
 
+MA_Z_HEADER, MA_Z_ISIZE, MA_Z_DATA, MA_Z_SHORT, MA_Z_CRC = 1, 2, 4, 8, 16
+MA_X_BAD_RECORD = 1
+
+
+class Bgzf(C.Structure):
+    """ma_bgzf_t: compressed BGZF members and where each begins"""
+    _fields_ = [("n_blocks", C.c_int64), ("cblob", C.c_void_p), ("cblob_bytes", C.c_uint64), ("blk_off", C.c_void_p),
+                ("blk_len", C.c_void_p)]
+
+
+class InflateOut(C.Structure):
+    """ma_inflate_out_t: the capacity, then five arrays -- all required"""
+    _fields_ = [("raw_cap", C.c_uint64)] + [(n, C.c_void_p) for n in ("raw", "blk_raw_off", "blk_state", "n_raw", "n_flagged")]
+
+
+class RecordStreams(C.Structure):
+    """ma_record_streams_t: inflated BAM bytes and the byte ranges whose records are wanted"""
+    _fields_ = [("raw", C.c_void_p), ("raw_bytes", C.c_uint64), ("n_streams", C.c_int64), ("str_begin", C.c_void_p),
+                ("str_end", C.c_void_p)]
+
+
+class IndexOut(C.Structure):
+    """ma_index_out_t: the capacity, then eight arrays -- all required"""
+    _fields_ = [("rec_cap", C.c_uint64)] + [(n, C.c_void_p) for n in (
+        "n_found", "str_rec_off", "str_state", "rec_off", "rec_len", "rec_ref", "rec_pos", "rec_span")]
+
+
+BGZF_DTYPES = dict(cblob=np.uint8, blk_off=np.uint64, blk_len=np.uint32)
+STREAMS_DTYPES = dict(raw=np.uint8, str_begin=np.uint64, str_end=np.uint64)
+
+
+def inflate_out_spec(n_blocks, raw_cap):
+    """arrays of ma_inflate_out_t (ma_inflate_blocks_batch)"""
+    n = int(n_blocks)
+    return dict(raw=(np.uint8, int(raw_cap)), blk_raw_off=(np.uint64, n + 1), blk_state=(np.uint8, n), n_raw=(np.uint64, 1),
+                n_flagged=(np.uint64, 1))
+
+
+def index_out_spec(n_streams, rec_cap):
+    """arrays of ma_index_out_t (ma_index_records_batch)"""
+    n, r = int(n_streams), int(rec_cap)
+    return dict(n_found=(np.uint64, 1), str_rec_off=(np.uint64, n + 1), str_state=(np.uint8, n), rec_off=(np.uint64, r),
+                rec_len=(np.uint32, r), rec_ref=(np.int32, r), rec_pos=(np.int32, r), rec_span=(np.uint32, r))
+
+
+def make_bgzf_struct(arrays, n_blocks, cblob_bytes):
+    """ma_bgzf_t over a dict of arrays (numpy, torch tensors or raw pointers; kept alive by the caller)"""
+    s = fill_struct(Bgzf, arrays)
+    s.n_blocks, s.cblob_bytes = int(n_blocks), int(cblob_bytes)
+    return s
+
+
+def make_inflate_out(arrays, raw_cap):
+    s = fill_struct(InflateOut, arrays)
+    s.raw_cap = int(raw_cap)
+    return s
+
+
+def make_streams_struct(arrays, n_streams, raw_bytes):
+    """ma_record_streams_t over a dict of arrays (numpy, torch tensors or raw pointers; kept alive by the caller)"""
+    s = fill_struct(RecordStreams, arrays)
+    s.n_streams, s.raw_bytes = int(n_streams), int(raw_bytes)
+    return s
+
+
+def make_index_out(arrays, rec_cap):
+    s = fill_struct(IndexOut, arrays)
+    s.rec_cap = int(rec_cap)
+    return s
+
+
 def gate_out_spec(n):
     return dict(max_approx=(np.uint32, n), max_exact=(np.uint32, n))
 

@@ -1343,6 +1343,12 @@ void ma_destroy(ma_ctx_t* ctx) {
   ctx->sl_ws.release();
   for (auto& bf : ctx->sl_in) bf.release();
   for (auto& bf : ctx->sl_out) bf.release();
+  ctx->inf_ws.release();
+  ctx->idx_ws.release();
+  for (auto& bf : ctx->inf_in) bf.release();
+  for (auto& bf : ctx->inf_out) bf.release();
+  for (auto& bf : ctx->idx_in) bf.release();
+  for (auto& bf : ctx->idx_out) bf.release();
   ctx->poa_cause.release();
   for (auto& pp : ctx->pin) {
     if (pp) (void)hipHostFree(pp);
@@ -1812,6 +1818,129 @@ int ma_select_records_batch(ma_ctx_t* ctx, const ma_records_t* in, const ma_sele
   }
   if (host) {
     std::vector<OutItem> const oi = out_items(st[2]);
+    for (size_t i = 0; i < oi.size(); ++i)
+      if (oi[i].bytes) MA_HIP(ctx, hipMemcpyAsync(oi[i].user, *oi[i].dev, oi[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(ctx, ma_stream_sync(ctx));
+  }
+  return MA_OK;
+}
+
+namespace {
+// the arrays of a MA_MEM_HOST call of the two entry points below: where the kernels find them, the caller's, the bytes
+struct StageIn { const void* src; size_t bytes; const void** dst; };
+struct StageOut { void** dev; void* user; size_t bytes; };
+const void** cslot(const void* p) { return static_cast<const void**>(const_cast<void*>(p)); }  // p: the address of a pointer member
+void** slot(void* p) { return static_cast<void**>(p); }
+}  // namespace
+
+int ma_inflate_blocks_batch(ma_ctx_t* ctx, const ma_bgzf_t* in, const ma_inflate_out_t* out) {
+  MA_BEGIN(ctx);
+  if (!in || !out || in->n_blocks < 0) return MA_ERR_ARG;
+  if (!in->cblob || !in->blk_off || !in->blk_len) return MA_ERR_ARG;
+  if (!out->raw || !out->blk_raw_off || !out->blk_state || !out->n_raw || !out->n_flagged) return MA_ERR_ARG;
+  if (in->n_blocks > 0x7FFFFFFFll) {
+    ma_set_err(ctx, "ma_inflate_blocks_batch: more than 2^31 - 1 blocks in one batch");
+    return MA_ERR_PARAM;
+  }
+  size_t const n = static_cast<size_t>(in->n_blocks);
+  bool const host = ctx->memspace == MA_MEM_HOST;
+  ma_bgzf_t din = *in;
+  ma_inflate_out_t dout = *out;
+  // (no block's payload is more than 64 KiB, whatever the caller's capacity)
+  size_t const raw_room = static_cast<size_t>(std::min<u64>(out->raw_cap, 65536ull * n));
+  auto out_items = [&](u64 raw_bytes) {
+    return std::vector<StageOut>{{slot(&dout.raw), out->raw, static_cast<size_t>(raw_bytes)}, {slot(&dout.blk_raw_off), out->blk_raw_off, 8 * (n + 1)},
+                                 {slot(&dout.blk_state), out->blk_state, n}, {slot(&dout.n_raw), out->n_raw, 8},
+                                 {slot(&dout.n_flagged), out->n_flagged, 8}};
+  };
+  if (host) {
+    StageIn const items[3] = {{in->cblob, static_cast<size_t>(in->cblob_bytes), cslot(&din.cblob)},
+                              {in->blk_off, 8 * n, cslot(&din.blk_off)},
+                              {in->blk_len, 4 * n, cslot(&din.blk_len)}};
+    for (int i = 0; i < 3; ++i) {
+      MA_HIP(ctx, ctx->inf_in[i].reserve(items[i].bytes + 16));
+      if (items[i].bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->inf_in[i].p, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+      *items[i].dst = ctx->inf_in[i].p;
+    }
+    std::vector<StageOut> const oi = out_items(raw_room);
+    for (size_t i = 0; i < oi.size(); ++i) {
+      MA_HIP(ctx, ctx->inf_out[i].reserve(oi[i].bytes + 16));
+      *oi[i].dev = ctx->inf_out[i].p;
+    }
+  }
+  u64 st[4] = {0, 0, 0, 0};
+  MA_TRY(launch_inflate(ctx, din, dout, st));
+  if (st[0] != ~0ull) {
+    ma_set_err(ctx, "ma_inflate_blocks_batch: block " + std::to_string(st[0]) + " does not lie inside cblob (blk_off + blk_len passes cblob_bytes)");
+    return MA_ERR_ARG;
+  }
+  if (st[1] & 1u) {
+    if (host) *out->n_raw = st[2];
+    ma_set_err(ctx, "ma_inflate_blocks_batch: raw_cap " + std::to_string(out->raw_cap) + " is under the " + std::to_string(st[2]) +
+                        " bytes needed (*n_raw)");
+    return MA_ERR_ARG;
+  }
+  if (host) {
+    std::vector<StageOut> const oi = out_items(st[2]);
+    for (size_t i = 0; i < oi.size(); ++i)
+      if (oi[i].bytes) MA_HIP(ctx, hipMemcpyAsync(oi[i].user, *oi[i].dev, oi[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(ctx, ma_stream_sync(ctx));
+  }
+  return MA_OK;
+}
+
+int ma_index_records_batch(ma_ctx_t* ctx, const ma_record_streams_t* in, const ma_index_out_t* out) {
+  MA_BEGIN(ctx);
+  if (!in || !out || in->n_streams < 0) return MA_ERR_ARG;
+  if (!in->raw || !in->str_begin || !in->str_end) return MA_ERR_ARG;
+  if (!out->n_found || !out->str_rec_off || !out->str_state || !out->rec_off || !out->rec_len || !out->rec_ref || !out->rec_pos || !out->rec_span)
+    return MA_ERR_ARG;
+  if (in->n_streams > 0x7FFFFFFFll) {
+    ma_set_err(ctx, "ma_index_records_batch: more than 2^31 - 1 streams in one batch");
+    return MA_ERR_PARAM;
+  }
+  size_t const n = static_cast<size_t>(in->n_streams);
+  bool const host = ctx->memspace == MA_MEM_HOST;
+  ma_record_streams_t din = *in;
+  ma_index_out_t dout = *out;
+  // (a record takes 36 bytes or more; overlapping streams list a record once each)
+  size_t const rec_room = static_cast<size_t>(std::min<u64>(out->rec_cap, (in->raw_bytes / 36u + 1u) * std::max<u64>(n, 1)));
+  auto out_items = [&](u64 recs) {
+    size_t const r = static_cast<size_t>(recs);
+    return std::vector<StageOut>{{slot(&dout.n_found), out->n_found, 8}, {slot(&dout.str_rec_off), out->str_rec_off, 8 * (n + 1)},
+                                 {slot(&dout.str_state), out->str_state, n}, {slot(&dout.rec_off), out->rec_off, 8 * r},
+                                 {slot(&dout.rec_len), out->rec_len, 4 * r}, {slot(&dout.rec_ref), out->rec_ref, 4 * r},
+                                 {slot(&dout.rec_pos), out->rec_pos, 4 * r}, {slot(&dout.rec_span), out->rec_span, 4 * r}};
+  };
+  if (host) {
+    StageIn const items[3] = {{in->raw, static_cast<size_t>(in->raw_bytes), cslot(&din.raw)},
+                              {in->str_begin, 8 * n, cslot(&din.str_begin)},
+                              {in->str_end, 8 * n, cslot(&din.str_end)}};
+    for (int i = 0; i < 3; ++i) {
+      MA_HIP(ctx, ctx->idx_in[i].reserve(items[i].bytes + 16));
+      if (items[i].bytes) MA_HIP(ctx, hipMemcpyAsync(ctx->idx_in[i].p, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+      *items[i].dst = ctx->idx_in[i].p;
+    }
+    std::vector<StageOut> const oi = out_items(rec_room);
+    for (size_t i = 0; i < oi.size(); ++i) {
+      MA_HIP(ctx, ctx->idx_out[i].reserve(oi[i].bytes + 16));
+      *oi[i].dev = ctx->idx_out[i].p;
+    }
+  }
+  u64 st[4] = {0, 0, 0, 0};
+  MA_TRY(launch_index(ctx, din, dout, st));
+  if (st[0] != ~0ull) {
+    ma_set_err(ctx, "ma_index_records_batch: stream " + std::to_string(st[0]) + " has str_begin > str_end or str_end > raw_bytes");
+    return MA_ERR_ARG;
+  }
+  if (st[1] & 1u) {
+    if (host) *out->n_found = st[2];
+    ma_set_err(ctx, "ma_index_records_batch: rec_cap " + std::to_string(out->rec_cap) + " is under the " + std::to_string(st[2]) +
+                        " records found (*n_found)");
+    return MA_ERR_ARG;
+  }
+  if (host) {
+    std::vector<StageOut> const oi = out_items(st[2]);
     for (size_t i = 0; i < oi.size(); ++i)
       if (oi[i].bytes) MA_HIP(ctx, hipMemcpyAsync(oi[i].user, *oi[i].dev, oi[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(ctx, ma_stream_sync(ctx));

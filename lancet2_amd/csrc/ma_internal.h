@@ -151,6 +151,8 @@ struct ma_ctx {
   bool fl_lds_set = false;  // the large sort's dynamic-LDS attribute is set on this context's device
   // ma_select_records_batch: its workspace (select.hip) and, for a MA_MEM_HOST call, the staged input and output arrays
   ma::DevBuf sl_ws, sl_in[6], sl_out[10];
+  // ma_inflate_blocks_batch / ma_index_records_batch: their workspaces (inflate.hip) and, for a MA_MEM_HOST call, the staged arrays
+  ma::DevBuf inf_ws, inf_in[3], inf_out[5], idx_ws, idx_in[3], idx_out[8];
   unsigned long long poa_export_counts[4] = {0, 0, 0, 0};
   hipEvent_t sync_ev = nullptr;  // blocking-sync event: host threads sleep instead of spinning while the stream drains
   // host route (MA_MEM_HOST) of ma_process_batch, per lane: packed result records (pack.hip) and their pinned landing area
@@ -270,6 +272,11 @@ int launch_flatten(ma_ctx* ctx, const ma_records_t& in, const ma_flat_out_t& out
 // ma_select_records_batch on device pointers (select.hip), likewise -- status[0] the first bad record (~0: none), [1] bit 0 a
 // bad rec_win_off, [2] the records selected, [3] the windows with one of MA_S_HOST_BITS
 int launch_select(ma_ctx* ctx, const ma_records_t& in, const ma_select_params_t& sp, const ma_select_out_t& out, u64* status);
+// ma_inflate_blocks_batch / ma_index_records_batch on device pointers (inflate.hip), likewise -- status[0] the first block
+// outside the blob / the first stream with bad bounds (~0: none), [1] bit 0 the capacity is under the need, [2] the need (bytes
+// of raw / records), [3] the flagged blocks / streams
+int launch_inflate(ma_ctx* ctx, const ma_bgzf_t& in, const ma_inflate_out_t& out, u64* status);
+int launch_index(ma_ctx* ctx, const ma_record_streams_t& in, const ma_index_out_t& out, u64* status);
 
 int launch_gate(ma_ctx* ctx, const DBatch& b, u32* max_approx, u32* max_exact);
 int launch_assemble(ma_ctx* ctx, const DBatch& b, const ma_asm_out_t& o, const u32* gate_approx);

@@ -64,6 +64,9 @@ def load_library(path=None):
         lib.ma_flatten_records_batch.argtypes = [C.c_void_p] * 3
     if hasattr(lib, "ma_select_records_batch"):  # (likewise: a build of before the record selection)
         lib.ma_select_records_batch.argtypes = [C.c_void_p] * 4
+    if hasattr(lib, "ma_inflate_blocks_batch"):  # (likewise: a build of before the device inflate)
+        lib.ma_inflate_blocks_batch.argtypes = [C.c_void_p] * 3
+        lib.ma_index_records_batch.argtypes = [C.c_void_p] * 3
     return lib
 
 
@@ -270,6 +273,71 @@ class Engine:
         rc = self.lib.ma_select_records_batch(self.h, C.byref(records_struct), C.byref(select_params), C.byref(select_out))
         if rc != 0:
             e = EngineError(f"ma_select_records_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+
+    def inflate_blocks(self, cblob, blk_off, blk_len, raw_cap=None):
+        """ma_inflate_blocks_batch: BGZF members of `cblob` -> dict of the capi.inflate_out_spec arrays, raw cut to n_raw.
+        Without raw_cap the call is re-submitted once with the need it reported.  Raises EngineError with .rc = the
+        ma_error and .arrays = the arrays as the call left them."""
+        ins = dict(cblob=np.ascontiguousarray(cblob, dtype=np.uint8), blk_off=np.ascontiguousarray(blk_off, dtype=np.uint64),
+                   blk_len=np.ascontiguousarray(blk_len, dtype=np.uint32))
+        n = len(ins["blk_off"])
+        cap = int(raw_cap) if raw_cap is not None else 4 * ins["cblob"].size
+        while True:
+            out = self._alloc(capi.inflate_out_spec(n, cap))
+            # (an empty array has no address worth passing: every member is required to be non-NULL)
+            held = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in list(ins.items()) + list(out.items())}
+            try:
+                self.inflate_blocks_device(capi.make_bgzf_struct(held, n, ins["cblob"].size), capi.make_inflate_out(held, cap))
+            except EngineError as e:
+                need = int(held["n_raw"][0])
+                if raw_cap is None and e.rc == capi.MA_ERR_ARG and need > cap:
+                    cap = need
+                    continue
+                e.arrays = dict(out, n_raw=held["n_raw"], n_flagged=held["n_flagged"])
+                raise
+            out["n_raw"], out["n_flagged"] = held["n_raw"], held["n_flagged"]
+            out["raw"] = out["raw"][:int(held["n_raw"][0])]
+            return out
+
+    def inflate_blocks_device(self, bgzf_struct, inflate_out):
+        """ma_inflate_blocks_batch on caller-made structs (either memory space)"""
+        rc = self.lib.ma_inflate_blocks_batch(self.h, C.byref(bgzf_struct), C.byref(inflate_out))
+        if rc != 0:
+            e = EngineError(f"ma_inflate_blocks_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+
+    def index_records(self, raw, str_begin, str_end, rec_cap=None):
+        """ma_index_records_batch: the records of byte ranges of `raw` -> dict of the capi.index_out_spec arrays, the five
+        rec_ arrays cut to n_found.  Without rec_cap the call is re-submitted once with the need it reported."""
+        ins = dict(raw=np.ascontiguousarray(raw, dtype=np.uint8), str_begin=np.ascontiguousarray(str_begin, dtype=np.uint64),
+                   str_end=np.ascontiguousarray(str_end, dtype=np.uint64))
+        n = len(ins["str_begin"])
+        cap = int(rec_cap) if rec_cap is not None else ins["raw"].size // 256 + 16
+        while True:
+            out = self._alloc(capi.index_out_spec(n, cap))
+            held = {k: (v if v.size else np.zeros(1, v.dtype)) for k, v in list(ins.items()) + list(out.items())}
+            try:
+                self.index_records_device(capi.make_streams_struct(held, n, ins["raw"].size), capi.make_index_out(held, cap))
+            except EngineError as e:
+                need = int(held["n_found"][0])
+                if rec_cap is None and e.rc == capi.MA_ERR_ARG and need > cap:
+                    cap = need
+                    continue
+                e.arrays = dict(out, n_found=held["n_found"])
+                raise
+            out["n_found"] = held["n_found"]
+            for k in ("rec_off", "rec_len", "rec_ref", "rec_pos", "rec_span"):
+                out[k] = out[k][:int(held["n_found"][0])]
+            return out
+
+    def index_records_device(self, streams_struct, index_out):
+        """ma_index_records_batch on caller-made structs (either memory space)"""
+        rc = self.lib.ma_index_records_batch(self.h, C.byref(streams_struct), C.byref(index_out))
+        if rc != 0:
+            e = EngineError(f"ma_index_records_batch failed ({rc}): {self.lib.ma_last_error(self.h).decode()}")
             e.rc = rc
             raise e
 
